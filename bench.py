@@ -11,14 +11,22 @@ samples_per_gpu = 2 (config :104), synthetic nuScenes-shaped inputs (seeded,
 resident in HBM before the timed region), fp32-equivalent arithmetic.
 
 One "step" = the whole path over one batch on every rank; value = samples/s over
-all ranks.  Rank 0 prints ONE JSON line.  At N = 1 the line also carries
-  roofline      the dominant conv kernel, timed live with HIP events
+all ranks, ms_per_step = wall time of one timed step.  Rank 0 prints ONE JSON line.
+A plain run sets up, warms up, times K steps, writes --dump-outputs and prints the line:
+nothing else.  With --full the line also carries (at N = 1)
+  roofline      the dominant conv kernel, timed live with HIP events (--no-profile: not)
   cpu_baseline  the oracle port of the same path on the host cores (bounded sample)
   also          the same measurement for configs[1] (TransFusion-L voxel backbone,
-                4 clouds/GPU, everything trained) -- a secondary line, not the headline.
+                4 clouds/GPU, everything trained) and the other secondary workloads /
+                precisions, each in a process of its own -- secondary lines, not the headline
+and an untimed sanity step checks every parameter and gradient after the timed steps.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload lc|transfusion_l]
-                    [--no-cpu-baseline] [--no-also] [--no-profile]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-also] [--no-profile]]
+
+--dump-outputs DIR: what the last timed step handed back (see dump_outputs) as .npy files.
+The timed steps start from the seeded initial state whatever the time-based settle phase
+took, so with the same arguments two builds can be compared output for output.
 
 `--gpus N` started as a plain process re-launches itself as N ranks under
 torch.distributed.run (one process per GPU, RCCL over xGMI); started by
@@ -142,6 +150,11 @@ def parse():
                          "transfusion_l = configs[1], the LiDAR-only voxel backbone")
     ap.add_argument("--no-profile", action="store_true",
                     help="skip per-launch event timing of the conv kernels")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, the CPU baseline, the secondary workloads "
+                         "and run the sanity step (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -416,6 +429,47 @@ def mean_of_product(bev, target):
     return torch.dot(a, b) / a.numel()
 
 
+DUMP_SAMPLE = 1 << 22      # elements kept of a larger module output: 16 MB of float32
+DUMP_PARAMS = 1 << 23      # trainable parameters kept whole up to this count (32 MB)
+
+
+def _flat_sample(flat, limit, seed):
+    """1-D `flat` whole when it has at most `limit` elements, else the elements at `limit`
+    sorted positions drawn by a generator seeded with `seed` -> (float32 numpy, sampled)."""
+    n = flat.numel()
+    if n <= limit:
+        return flat.float().cpu().numpy(), False
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    pos = torch.randint(n, (limit,), generator=g).sort().values
+    return flat[pos.to(flat.device)].float().cpu().numpy(), True
+
+
+def dump_outputs(path, loss, out, params):
+    """--dump-outputs: what the last timed step handed back, as float32 / float64 .npy files
+    under `path` (~50 MB at most):
+      loss                the step's loss (float64, shape [1]);
+      output              the module's output (the BEV map), flattened in logical (NCHW)
+                          order -- or output_sample, DUMP_SAMPLE elements of it at seeded
+                          positions, and for a 4-D map output_channel_sum, the float64 sum
+                          over H x W of every channel of every sample;
+      params              the trainable parameters as the step's AdamW update left them,
+                          concatenated in named_parameters() order -- or params_sample."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = out.detach()
+    arrays = {"loss": np.array([float(loss.item())], np.float64)}
+    a, sampled = _flat_sample(out.contiguous().reshape(-1), DUMP_SAMPLE, 0)
+    arrays["output_sample" if sampled else "output"] = a
+    if out.dim() == 4:
+        arrays["output_channel_sum"] = out.sum(dim=(2, 3), dtype=torch.float64).cpu().numpy()
+    a, sampled = _flat_sample(torch.cat([p.detach().reshape(-1) for p in params]), DUMP_PARAMS, 1)
+    arrays["params_sample" if sampled else "params"] = a
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def lc_worker_init(sample_ids, seed):
     """Runs in the index worker process (msmdfusion_amd/prefetch_proc.py): the synthetic
     data source and the index half of the LC step.  Weights play no part in prepare();
@@ -564,9 +618,18 @@ def run_workload(workload, args, dev, rank, world, profile):
                                        # thread to submit it
                                        depth=int(os.environ.get("MSMD_PREFETCH_DEPTH", "2")),
                                        workers=int(os.environ.get("MSMD_PREFETCH_WORKERS", "1")) or None)
+    # the seeded initial state, restored after the settle phase (below)
+    state = list(model.parameters()) + list(model.buffers())
+    initial = [t.detach().clone() for t in state]
+    last = {}           # the module output of the step run with last["keep"] set
+    last["keep"] = False
+
+    def loss_of(bev):
+        if last["keep"]:
+            last["out"] = bev
+        return mean_of_product(bev, target)
     # grad_clip max_norm=10 (config); the step structure is msmdfusion_amd.distributed.TrainStep
-    train_step = D.TrainStep(net, params, opt, lambda bev: mean_of_product(bev, target), prefetch,
-                             10.0)
+    train_step = D.TrainStep(net, params, opt, loss_of, prefetch, 10.0)
     calls = [0]          # every step of this workload, timed or not (profile normalisation)
 
     def step(b):
@@ -595,6 +658,29 @@ def run_workload(workload, args, dev, rank, world, profile):
     settle_s = float(os.environ.get("MSMD_BENCH_SETTLE_S", "1.5"))
     D.settle_steps(lambda: step(batch), wl["settle"] if (lc or prefetch is not None) else 2,
                    settle_s, device=dev)      # same count on every rank (each step all-reduces)
+    # The settle phase lasts a TIME, so the number of AdamW updates it made depends on the
+    # speed of the build: back to the seeded initial state -- parameters, buffers (BatchNorm
+    # statistics), a fresh AdamW, the host RNG the step draws its dummy embedding from (in
+    # the index pass: drained first) -- so that what the timed steps compute is a function of
+    # the arguments alone (--dump-outputs compares two builds).  Then two steps refill the
+    # index pipeline the drain emptied (a fixed count: the state stays a function of them).
+    from msmdfusion_amd.spconv.functional import invalidate_packed_weights
+    train_step.drain()
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        for t, v in zip(state, initial):
+            t.copy_(v)          # in place: moves _version, so the packed weight images go stale
+        for st in opt.state.values():       # zero moments at step 0: a fresh AdamW
+            for k, v in st.items():
+                if torch.is_tensor(v):
+                    v.zero_()
+                else:
+                    st[k] = 0
+    invalidate_packed_weights()
+    torch.manual_seed(0)
+    del initial
+    for _ in range(2):
+        step(batch)
     torch.cuda.synchronize()
     for _ in range(args.warmup):
         step(batch)
@@ -621,10 +707,12 @@ def run_workload(workload, args, dev, rank, world, profile):
     torch.cuda.synchronize()
     D.barrier()
     t0 = time.perf_counter()
+    keep_last = bool(args.dump_outputs)
     for i in range(args.steps):
         if i in sampled:
             marks.append(len(prof))
         K.PROFILE = prof if i in sampled else None
+        last["keep"] = keep_last and i == args.steps - 1
         loss = step(batch)
     torch.cuda.synchronize()
     D.barrier()
@@ -634,41 +722,48 @@ def run_workload(workload, args, dev, rank, world, profile):
         main_ctx.__exit__(None, None, None)
     elapsed = D.global_max(elapsed, device=dev)
     assert torch.isfinite(loss).item()
-    # untimed sanity step: every parameter and every gradient of the trained modules is
-    # finite (a skipped tile or a stale buffer shows up as NaN/garbage here, not in the rate)
-    loss = None
     train_step.drain()      # (the index work queued ahead of the last step: see TrainStep.drain)
     torch.cuda.synchronize()
-    bev = net(*batch)
-    mean_of_product(bev, target).backward()
-    bad = []
-    for n, p in model.named_parameters():
-        if p.requires_grad and p.grad is None and "blocks_2D" not in n and "blocks_mix" not in n:
-            bad.append((n, "no gradient"))
-        elif p.grad is not None and not torch.isfinite(p.grad).all():
-            bad.append((n, "%d non-finite gradient entries" % int((~torch.isfinite(p.grad)).sum())))
-        if not torch.isfinite(p).all():
-            bad.append((n, "%d non-finite entries" % int((~torch.isfinite(p)).sum())))
-    assert not bad, "workload %s: %d bad parameters after the timed steps: %s" % (
-        workload, len(bad), bad[:8])
-    opt.zero_grad(set_to_none=True)
+    if keep_last and rank == 0:
+        dump_outputs(args.dump_outputs, loss, last["out"], params)
+    last.clear()
+    loss = None
+    if args.full:
+        # untimed sanity step: every parameter and every gradient of the trained modules is
+        # finite (a skipped tile or a stale buffer shows up as NaN/garbage here, not in the rate)
+        bev = net(*batch)
+        mean_of_product(bev, target).backward()
+        bad = []
+        for n, p in model.named_parameters():
+            if p.requires_grad and p.grad is None and "blocks_2D" not in n \
+                    and "blocks_mix" not in n:
+                bad.append((n, "no gradient"))
+            elif p.grad is not None and not torch.isfinite(p.grad).all():
+                bad.append((n, "%d non-finite gradient entries"
+                            % int((~torch.isfinite(p.grad)).sum())))
+            if not torch.isfinite(p).all():
+                bad.append((n, "%d non-finite entries" % int((~torch.isfinite(p)).sum())))
+        assert not bad, "workload %s: %d bad parameters after the timed steps: %s" % (
+            workload, len(bad), bad[:8])
+        opt.zero_grad(set_to_none=True)
+        del bev
     n_samples = args.steps * spg * world
     res = {"value": round(n_samples / elapsed, 3), "unit": "samples/s",
            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
            "config": {"workload": wl["name"], "global_batch": spg * world,
                       "parallelism": "dp%d" % world, "index_prefetch": prefetch is not None,
                       "trainable_params": sum(p.numel() for p in params)}}
-    if workload == "lc_img":
+    if workload == "lc_img" and args.full:
         res["image_glue"] = image_glue_kernel_times(model, batch)
-    if workload == "lc_quirks":
+    if workload == "lc_quirks" and args.full:
         res["modality_split"] = modality_split_times(model, batch)
     res["roofline"] = roofline(prof, workload, marks) if prof else None
     if res["roofline"]:
         r = res["roofline"]
         r["step_frac"] = round(r["step_gflop"] / res["ms_per_step"] / r["peak_tflops"], 4)
     if rank == 0:   # tools/stream_prof.py divides a rocprofv3 trace of this run by this count
-        print("[bench] workload=%s steps_total=%d (+1 untimed check step)" % (workload, calls[0]),
-              file=sys.stderr)
+        print("[bench] workload=%s steps_total=%d%s" % (
+            workload, calls[0], " (+1 untimed check step)" if args.full else ""), file=sys.stderr)
     if hasattr(prefetch, "close"):
         prefetch.close()
     del step, net, model, opt, prefetch
@@ -698,7 +793,7 @@ def main():
     sched_flags = device_schedule_flags()     # of THIS rank's device (0x4 = blocking waits)
     D.init_distributed(device=dev)      # RCCL (torch backend "nccl") when world > 1
 
-    head = run_workload(args.workload, args, dev, rank, world, not args.no_profile)
+    head = run_workload(args.workload, args, dev, rank, world, args.full and not args.no_profile)
     out = None
     if rank == 0:
         out = {"metric": WORKLOADS[args.workload]["metric"], "value": head["value"],
@@ -718,23 +813,23 @@ def main():
         for extra in ("image_glue", "modality_split"):
             if extra in head:
                 out[extra] = head[extra]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(
                 args.workload, budget_s=float(os.environ.get("MSMD_BENCH_CPU_BUDGET", "14.0")))
-    if world == 1 and not args.no_also and args.workload == "lc":
+    if world == 1 and args.full and not args.no_also and args.workload == "lc":
         # secondary lines: a leg that fails reports its error instead of costing the headline
         out["also"] = {}
 
         def leg(key, wl, profile=False, dtype=None, cpu=False):
             """One secondary workload in a process of its own (this script again, `--workload
-            wl --no-also`): what an earlier leg leaves behind in the process -- allocator
+            wl --full --no-also`): what an earlier leg leaves behind in the process -- allocator
             pools, cached dense-grid tables, worker threads, packed-weight images -- costs the
             later B = 2 legs up to 20 % (round 6: the same leg read 214, 194 or 174 samples/s
             depending on how many legs had run before it; 205-213 in a fresh process), so
             every line is measured the way the headline is: first in its process."""
             import subprocess
-            cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--no-also",
-                   "--steps", str(args.steps), "--warmup", str(args.warmup)]
+            cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--full",
+                   "--no-also", "--steps", str(args.steps), "--warmup", str(args.warmup)]
             if not profile:
                 cmd.append("--no-profile")
             if not cpu:

@@ -16,7 +16,7 @@ for w in $WHAT; do
       timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -150 > $OUT/gpu_tests.log
       tail -3 $OUT/gpu_tests.log ;;
     bench)
-      timeout 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+      timeout 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
       tail -c 600 $OUT/bench_default.json; tail -3 $OUT/bench_default.err ;;
     prof)
       for wl in lc transfusion_l; do bash $R/tools/prof_bench.sh $TAG $wl; done ;;
@@ -25,8 +25,8 @@ for w in $WHAT; do
       cut -c1-200 $OUT/rulebook_voxelize_roofline.jsonl
       timeout 120 python tools/fps_bench.py 2>/dev/null | grep -v amdgpu.ids > $OUT/fps.txt; cat $OUT/fps.txt ;;
     cpu2)   # one rank on the two CPUs plan_rank_cpus grants at 8 ranks per 16-CPU node
-      MSMD_PIN_CPUS=0,1 MSMD_CPU_QUOTA=2 timeout 300 taskset -c 0,1 python bench.py --no-also --no-cpu-baseline > $OUT/bench_2cpu.json 2> $OUT/bench_2cpu.err
-      timeout 300 python bench.py --no-also --no-cpu-baseline > $OUT/bench_4cpu.json 2> $OUT/bench_4cpu.err
+      MSMD_PIN_CPUS=0,1 MSMD_CPU_QUOTA=2 timeout 300 taskset -c 0,1 python bench.py --full --no-also --no-cpu-baseline > $OUT/bench_2cpu.json 2> $OUT/bench_2cpu.err
+      timeout 300 python bench.py --full --no-also --no-cpu-baseline > $OUT/bench_4cpu.json 2> $OUT/bench_4cpu.err
       python -c "
 import json
 for n in ('2cpu', '4cpu'):

@@ -9,7 +9,7 @@ WL=${2:-lc}
 OUT=$R/gpurun_out/${1:-prof_cur}/prof_$WL
 mkdir -p $OUT
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o s -- \
-  python $R/bench.py --workload $WL --no-also --no-cpu-baseline --no-profile > $OUT/bench.json 2> $OUT/bench.err
+  python $R/bench.py --full --workload $WL --no-also --no-cpu-baseline --no-profile > $OUT/bench.json 2> $OUT/bench.err
 tail -c 300 $OUT/bench.json; echo
 t=$(find $OUT -name "*kernel_trace.csv" | head -1)
 f=$(find $OUT -name "*kernel_stats.csv" | head -1)

@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT; T=${1:-r05_final}; O=$R/gpurun_out/$T; mkdir -p $O; cd $R
 python -m pytest tests -m gpu -q 2>&1 | tail -8 > $O/tests.log
 python __graft_entry__.py smoke > $O/smoke.log 2>&1
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 bash tools/prof_bench.sh $T lc > $O/prof.log 2>&1
 bash tools/pmc_collect.sh lc $O/pmc_lc > $O/pmc.log 2>&1
 tail -2 $O/tests.log; tail -1 $O/smoke.log; python -c "

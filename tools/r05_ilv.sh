@@ -6,7 +6,7 @@ for ilv in 1 0; do
 done
 MSMD_LIB=$R/msmdfusion_amd/libmsmd_hip_prof.so MSMD_FWD_PP_MIN=97 python tools/kprof.py --lc > $O/kprof_ilv1.txt 2>&1
 for v in "1 161" "0 161" "1 97" "1 161" "0 161" "1 97"; do set -- $v
-  MSMD_FWD_ILV=$1 MSMD_FWD_PP_MIN=$2 python bench.py --no-also --no-cpu-baseline > $O/bench_ilv$1_min$2_$RANDOM.json 2>> $O/bench.err
+  MSMD_FWD_ILV=$1 MSMD_FWD_PP_MIN=$2 python bench.py --full --no-also --no-cpu-baseline > $O/bench_ilv$1_min$2_$RANDOM.json 2>> $O/bench.err
 done
 tail -3 $O/tests.log; grep -h "fwd" $O/layers_lc_ilv1.txt $O/layers_lc_ilv0.txt | cut -c1-150; grep -v amdgpu $O/kprof_ilv1.txt
 for f in $O/bench_ilv*.json; do python -c "

@@ -8,6 +8,6 @@ done
 MSMD_FWD_NT12=0 python tools/split_bench.py --lc > $O/layers_lc_pp1_nt12off.txt 2>&1
 MSMD_LIB=$R/msmdfusion_amd/libmsmd_hip_prof.so python tools/kprof.py --lc > $O/kprof_pp.txt 2>&1
 for pp in 1 0 1 0; do
-  MSMD_FWD_PP=$pp python bench.py --no-also --no-cpu-baseline > $O/bench_pp${pp}_$RANDOM.json 2>> $O/bench.err
+  MSMD_FWD_PP=$pp python bench.py --full --no-also --no-cpu-baseline > $O/bench_pp${pp}_$RANDOM.json 2>> $O/bench.err
 done
 tail -6 $O/tests.log; cat $O/layers_lc_pp1.txt $O/layers_lc_pp0.txt | grep -v amdgpu | cut -c1-200

@@ -4,7 +4,7 @@
 R=$GRAFT_REPO_ROOT; T=${1:-r06_final}; O=$R/gpurun_out/$T; mkdir -p $O; cd $R
 python -m pytest tests -m gpu -q 2>&1 | tail -8 > $O/tests.log
 python __graft_entry__.py smoke > $O/smoke.log 2>&1
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 for wl in lc transfusion_l; do bash tools/prof_bench.sh $T $wl > $O/prof_$wl.log 2>&1; done
 timeout 300 python tools/rulebook_bench.py 2>/dev/null > $O/rulebook_voxelize_roofline.jsonl
 timeout 120 python tools/fps_bench.py 2>/dev/null | grep -v amdgpu.ids > $O/fps.txt

@@ -1,7 +1,7 @@
 # image glue: NCHW maps / one conversion pass / channels-last convs -- glue ms + gather GB/s + step
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/r06c; mkdir -p $OUT; cd $R
 for m in 0 1 2; do
-  MSMD_GLUE_NHWC=$m timeout 400 python bench.py --workload lc_img --no-also --no-cpu-baseline --no-profile > $OUT/img_$m.json 2> $OUT/img_$m.err
+  MSMD_GLUE_NHWC=$m timeout 400 python bench.py --full --workload lc_img --no-also --no-cpu-baseline --no-profile > $OUT/img_$m.json 2> $OUT/img_$m.err
   python - <<PY
 import json
 d = json.load(open("$OUT/img_$m.json")); g = d["image_glue"]
