@@ -106,6 +106,63 @@ int msmd_voxel_mean(const float* voxels /* [M,max_points,C] */,
                     float* out /* [M,out_features] */, msmd_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * a1d  Dynamic voxelization + DynamicScatter (sum / mean / max, fwd + bwd)
+ * replaces: voxel_layer.dynamic_voxelize  mmdet3d/ops/voxel/src/voxelization.h:71-83
+ *           (CUDA mmdet3d/ops/voxel/src/voxelization_cuda.cu:25-61, 328-371)
+ *           voxel_layer.dynamic_point_to_voxel_forward  voxelization.h:96-108
+ *           (CUDA mmdet3d/ops/voxel/src/scatter_points_cuda.cu:246-306)
+ *           voxel_layer.dynamic_point_to_voxel_backward  voxelization.h:110-128
+ *           (CUDA mmdet3d/ops/voxel/src/scatter_points_cuda.cu:308-383)
+ *           DynamicVFE.map_voxel_center_to_point
+ *           mmdet3d/models/voxel_encoders/voxel_encoder.py:176-218
+ * ------------------------------------------------------------------------ */
+/* One (z, y, x) row per point, float32 floor((p-min)/size), grid = round((max-min)/size);
+ * out-of-range points get the reference kernel's pattern: x out of range writes -1 to slot
+ * 0 only, y to slots 0-1, z to slots 0-2; unwritten slots keep the caller's values.
+ * coors rows are `ndim` (>= 3) ints apart; slots 0-2 are the only ones touched. */
+int msmd_dynamic_voxelize(const float* points, int num_points, int num_features,
+                          const float* voxel_size /* host[3] x,y,z */,
+                          const float* coors_range /* host[6] */, int ndim,
+                          int32_t* coors /* [N, ndim] */, msmd_stream_t stream);
+
+/* Index half of a scatter: depends on the coordinates only.  A row is invalid when any of
+ * its ndim (1..8) entries is negative.  The M unique valid rows in lexicographic order go to
+ * voxel_coors rows [0, M); point2voxel[i] = row of point i or -1; the points of voxel v are
+ * seg_points[seg_start[v] .. seg_start[v+1]) in ascending point index; counts[v] = their
+ * number.  info[0] = M, info[1] = 1 when the packed 64-bit row key would not hold the
+ * columns' bit widths (then M = 0).  The caller reads info after the stream reaches here. */
+size_t msmd_scatter_index_workspace_bytes(int num_points);
+int msmd_scatter_index(const int32_t* coors /* [N, ndim] */, int num_points, int ndim,
+                       int32_t* voxel_coors /* [N, ndim] */, int32_t* point2voxel /* [N] */,
+                       int32_t* seg_points /* [N] */, int32_t* seg_start /* [N+1] */,
+                       int32_t* counts /* [N] */, int32_t* info /* [2] */, void* workspace,
+                       size_t workspace_bytes, msmd_stream_t stream);
+/* out[v, c] = sum (reduce 0) / mean (1) / max (2) of feats over segment v, accumulated in
+ * fp32 in ascending point index (no atomics: bitwise reproducible).  max also writes
+ * argmax[v, c] = the smallest point index attaining the maximum (argmax may be NULL). */
+int msmd_scatter_reduce_f32(const float* feats /* [N, C] */, int num_points, int num_channels,
+                            const int32_t* seg_points, const int32_t* seg_start, int num_voxels,
+                            int reduce, float* out /* [M, C] */, int32_t* argmax /* [M, C] */,
+                            msmd_stream_t stream);
+/* grad_in[i, c]: reduce 0 -> grad_out[v, c]; 1 -> grad_out[v, c] / counts[v]; 2 ->
+ * grad_out[v, c] where argmax[v, c] == i; 0 for other points and for point2voxel < 0. */
+int msmd_scatter_reduce_bwd_f32(const float* grad_out /* [M, C] */, int num_voxels,
+                                int num_points, int num_channels, const int32_t* point2voxel,
+                                const int32_t* counts, const int32_t* argmax, int reduce,
+                                float* grad_in /* [N, C] */, msmd_stream_t stream);
+/* The reference backward's traceback: argmax[v, c] = smallest point i of voxel v with
+ * feats[i, c] == reduced[v, c] (num_points where there is none). */
+int msmd_scatter_max_argmax_f32(const float* feats /* [N, C] */, int num_points,
+                                int num_channels, const int32_t* point2voxel,
+                                const float* reduced /* [M, C] */, int num_voxels,
+                                int32_t* argmax /* [M, C] */, msmd_stream_t stream);
+/* out[i, c] = voxel_feats[point2voxel[i], c], 0 where point2voxel[i] < 0.  Its backward is
+ * msmd_scatter_reduce_f32 (sum) on the same segments. */
+int msmd_scatter_gather_f32(const float* voxel_feats /* [M, C] */, int num_voxels,
+                            int num_channels, const int32_t* point2voxel, int num_points,
+                            float* out /* [N, C] */, msmd_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * a5  Submanifold rulebook (hash-based voxel index)
  * replaces: sparse_conv_ext.get_indice_pairs_3d(..., subM=1)
  *           mmdet3d/ops/spconv/src/all.cc:21-27,

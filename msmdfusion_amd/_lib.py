@@ -46,6 +46,13 @@ SIGNATURES = {
     "msmd_hard_voxelize_many_workspace_bytes": (_sz, [_vp, _i]),
     "msmd_hard_voxelize_many": (_i, [_vp, _i, _vp, _sz, _vp]),
     "msmd_voxel_mean": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "msmd_dynamic_voxelize": (_i, [_vp, _i, _i, _fp, _fp, _i, _vp, _vp]),
+    "msmd_scatter_index_workspace_bytes": (_sz, [_i]),
+    "msmd_scatter_index": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "msmd_scatter_reduce_f32": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "msmd_scatter_reduce_bwd_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "msmd_scatter_max_argmax_f32": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "msmd_scatter_gather_f32": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
     "msmd_rulebook_subm_workspace_bytes": (_sz, [_i]),
     "msmd_rulebook_subm3d": (_i, [_vp, _i, _i, _ip, _ip, _vp, _vp, _sz, _vp]),
     "msmd_rulebook_subm_bitmap_workspace_bytes": (_sz, [_i, _i, _ip]),

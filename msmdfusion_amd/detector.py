@@ -60,7 +60,12 @@ def _build_head(cfg, train_cfg, test_cfg, rows):
 @DETECTORS.register_module()
 class TransFusionDetector(nn.Module):
     """LiDAR-only detector (configs/transfusion_nusc_voxel_L.py): voxelize -> HardSimpleVFE ->
-    SparseEncoder -> SECOND -> SECONDFPN -> TransFusionHead."""
+    SparseEncoder -> SECOND -> SECONDFPN -> TransFusionHead.
+
+    A `pts_voxel_layer` with max_num_points=-1 (or max_voxels=-1) selects dynamic
+    voxelization (DynamicVoxelNet.voxelize, dynamic_voxelnet.py:46-71) with a dynamic voxel
+    encoder (DynamicSimpleVFE / DynamicVFE): every point keeps its voxel coordinates, the
+    encoder reduces them, and prepare() computes the scatters' index half up front."""
 
     def __init__(self, pts_voxel_layer=None, pts_voxel_encoder=None, pts_middle_encoder=None,
                  pts_backbone=None, pts_neck=None, pts_bbox_head=None, img_backbone=None,
@@ -103,7 +108,19 @@ class TransFusionDetector(nn.Module):
     with_img_backbone = property(lambda self: self.img_backbone is not None)
     with_img_neck = property(lambda self: self.img_neck is not None)
 
+    @property
+    def dynamic_voxelization(self):
+        return self.pts_voxel_layer.max_num_points == -1 or -1 in self.pts_voxel_layer.max_voxels
+
     # ---- the path ----------------------------------------------------------------------
+    @torch.no_grad()
+    def voxelize_dynamic(self, points):
+        """dynamic_voxelnet.py:46-71: per-sample dynamic voxelization, batch id prepended.
+        -> (points[N, C] concatenated, coors[N, 4] (b, z, y, x); -1 entries: out of range)"""
+        coors = [nn.functional.pad(self.pts_voxel_layer(p), (1, 0), mode="constant", value=b)
+                 for b, p in enumerate(points)]
+        return torch.cat(points, dim=0), torch.cat(coors, dim=0)
+
     @torch.no_grad()
     def voxelize(self, points):
         """transfusion.py:76-101: hard voxelization per sample, batch id prepended; the
@@ -118,13 +135,24 @@ class TransFusionDetector(nn.Module):
     def prepare(self, points):
         """The index-only part of a step (no weights, no previous step): voxelization and
         every rulebook / tiling / pair list of the encoder -- what IndexPrefetcher runs a
-        step ahead."""
+        step ahead.  Dynamic voxelization: the points, their coordinates and the scatter
+        index (whose voxel rows the encoder's rulebooks are built on) take the place of the
+        voxel features."""
+        if self.dynamic_voxelization:
+            from .dynamic_scatter import scatter_index
+            pts, coors = self.voxelize_dynamic(points)
+            index = scatter_index(coors.contiguous())
+            planned, _ = self.pts_middle_encoder.plan(index.voxel_coors, len(points))
+            return (pts, coors, index), index.voxel_coors, planned
         feats, coors = self.voxelize(points)
         planned, _ = self.pts_middle_encoder.plan(coors, len(points))
         return feats, coors, planned
 
     def extract_sparse_feat(self, points, prepared=None):
         feats, coors, planned = prepared if prepared is not None else self.prepare(points)
+        if self.dynamic_voxelization:
+            pts, pts_coors, index = feats
+            feats, coors = self.pts_voxel_encoder(pts, pts_coors, index=index)
         bev, _ = self.pts_middle_encoder(feats, coors, len(points), planned=planned)
         return bev
 

@@ -210,6 +210,162 @@ def voxel_mean(voxels, num_points, out_features=None):
     return out
 
 
+# ------------------------------------------------------------------ dynamic voxelization
+REDUCE_TYPES = {"sum": 0, "mean": 1, "max": 2}
+
+
+def _need_dtype(t, dtype, what):
+    if t.dtype != dtype:
+        raise RuntimeError("%s must be %s, got %s" % (what, dtype, t.dtype))
+
+
+def _reduce_code(reduce_type):
+    if reduce_type not in REDUCE_TYPES:
+        raise RuntimeError("do not support reduce type %r (sum, mean, max)" % (reduce_type,))
+    return REDUCE_TYPES[reduce_type]
+
+
+def dynamic_voxelize(points, voxel_size, coors_range, coors=None):
+    """voxel_layer.dynamic_voxelize (voxelization_cuda.cu:25-61): coors[N,3] (z,y,x) int32,
+    written in place when given (out-of-range points get the reference's -1 pattern, slots
+    it does not write keep their values); a zero-filled tensor otherwise."""
+    _need_cuda(points, coors)
+    _need_dtype(points, torch.float32, "points")
+    if points.dim() != 2 or points.shape[1] < 3 or not points.is_contiguous():
+        raise RuntimeError("points must be a contiguous [N, >=3] tensor")
+    n = points.shape[0]
+    if coors is None:
+        coors = torch.zeros((n, 3), dtype=torch.int32, device=points.device)
+    _need_dtype(coors, torch.int32, "coors")
+    if coors.dim() != 2 or coors.shape[0] != n or coors.shape[1] < 3 or not coors.is_contiguous():
+        raise RuntimeError("coors must be a contiguous [N, >=3] int32 tensor")
+    check(lib.msmd_dynamic_voxelize(_p(points), n, points.shape[1], float_arr(voxel_size),
+                                    float_arr(coors_range), coors.shape[1], _p(coors), _stream()),
+          "msmd_dynamic_voxelize")
+    return coors
+
+
+class ScatterIndex:
+    """The index half of a dynamic scatter, a function of the coordinates alone:
+    voxel_coors[M, NDim] (unique valid rows, lexicographic), point2voxel[N] (-1: invalid),
+    counts[M], and the segment table seg_points[N] / seg_start[M+1] (the points of voxel v in
+    ascending point index).  Every scatter / gather on the same coordinates reuses it."""
+
+    __slots__ = ("voxel_coors", "point2voxel", "seg_points", "seg_start", "counts",
+                 "num_points", "num_voxels")
+
+    def __init__(self, voxel_coors, point2voxel, seg_points, seg_start, counts):
+        self.voxel_coors, self.point2voxel = voxel_coors, point2voxel
+        self.seg_points, self.seg_start, self.counts = seg_points, seg_start, counts
+        self.num_points, self.num_voxels = point2voxel.shape[0], voxel_coors.shape[0]
+
+
+def scatter_index(coors):
+    """coors[N, NDim] int32 (NDim 1..8; 4 = batch, z, y, x) -> ScatterIndex.  One host read
+    (the voxel count), as hard_voxelize."""
+    _need_cuda(coors)
+    _need_dtype(coors, torch.int32, "coors")
+    if coors.dim() != 2 or not 1 <= coors.shape[1] <= 8 or not coors.is_contiguous():
+        raise RuntimeError("coors must be a contiguous [N, NDim] int32 tensor (NDim 1..8)")
+    n, nd = coors.shape
+    dev = coors.device
+    vc = torch.empty((n, nd), dtype=torch.int32, device=dev)
+    p2v = torch.empty((n,), dtype=torch.int32, device=dev)
+    seg = torch.empty((n,), dtype=torch.int32, device=dev)
+    start = torch.empty((n + 1,), dtype=torch.int32, device=dev)
+    counts = torch.empty((n,), dtype=torch.int32, device=dev)
+    info = torch.empty((2,), dtype=torch.int32, device=dev)
+    nbytes = lib.msmd_scatter_index_workspace_bytes(n)
+    ws = _ws(nbytes, dev)
+    check(lib.msmd_scatter_index(_p(coors), n, nd, _p(vc), _p(p2v), _p(seg), _p(start),
+                                 _p(counts), _p(info), _p(ws), nbytes, _stream()),
+          "msmd_scatter_index")
+    m, overflow = info.tolist()
+    if overflow:
+        raise RuntimeError("scatter_index: the coordinate columns need more than 63 key bits")
+    return ScatterIndex(vc[:m], p2v, seg, start[:m + 1], counts[:m])
+
+
+def _need_feats(feats, n, what="feats"):
+    _need_dtype(feats, torch.float32, what)
+    if feats.dim() != 2 or feats.shape[0] != n or not feats.is_contiguous():
+        raise RuntimeError("%s must be a contiguous [%d, C] float32 tensor" % (what, n))
+
+
+def scatter_reduce(feats, index, reduce_type):
+    """feats[N, C] -> (out[M, C], argmax[M, C] int32 | None): the segment reduce of
+    dynamic_point_to_voxel_forward, in ascending point index (bitwise reproducible)."""
+    code = _reduce_code(reduce_type)
+    _need_cuda(feats, index.point2voxel)
+    _need_feats(feats, index.num_points)
+    m, c = index.num_voxels, feats.shape[1]
+    out = torch.empty((m, c), dtype=torch.float32, device=feats.device)
+    arg = torch.empty((m, c), dtype=torch.int32, device=feats.device) if code == 2 else None
+    check(lib.msmd_scatter_reduce_f32(_p(feats), index.num_points, c, _p(index.seg_points),
+                                      _p(index.seg_start), m, code, _p(out), _p(arg), _stream()),
+          "msmd_scatter_reduce_f32")
+    return out, arg
+
+
+def scatter_reduce_backward(grad_out, point2voxel, reduce_type, counts=None, argmax=None,
+                            out=None):
+    """d feats[N, C] of scatter_reduce from d out[M, C] (0 for invalid points); written into
+    `out` (contiguous [N, C] float32) when given."""
+    code = _reduce_code(reduce_type)
+    _need_cuda(grad_out, point2voxel, counts, argmax)
+    _need_dtype(grad_out, torch.float32, "grad")
+    _need_dtype(point2voxel, torch.int32, "point2voxel")
+    g = grad_out.contiguous()
+    m, c = g.shape
+    n = point2voxel.shape[0]
+    if code == 1 and (counts is None or counts.dtype != torch.int32 or counts.shape[0] != m):
+        raise RuntimeError("mean backward needs counts[M] int32")
+    if code == 2 and (argmax is None or argmax.dtype != torch.int32 or tuple(argmax.shape) != (m, c)):
+        raise RuntimeError("max backward needs argmax[M, C] int32")
+    if out is None:
+        out = torch.empty((n, c), dtype=torch.float32, device=g.device)
+    else:
+        _need_cuda(out)
+        _need_feats(out, n, "grad_feats")
+        if out.shape[1] != c:
+            raise RuntimeError("grad_feats has %d channels, the voxel gradient %d" % (out.shape[1], c))
+    check(lib.msmd_scatter_reduce_bwd_f32(_p(g), m, n, c, _p(point2voxel.contiguous()),
+                                          _p(None if counts is None else counts.contiguous()),
+                                          _p(None if argmax is None else argmax.contiguous()),
+                                          code, _p(out), _stream()),
+          "msmd_scatter_reduce_bwd_f32")
+    return out
+
+
+def scatter_max_argmax(feats, point2voxel, reduced):
+    """The reference backward's traceback (max_reduce_traceback_scatter_idx_kernel):
+    argmax[M, C] = smallest point whose value equals the voxel's maximum."""
+    _need_cuda(feats, point2voxel, reduced)
+    n = point2voxel.shape[0]
+    _need_feats(feats, n)
+    _need_dtype(reduced, torch.float32, "reduced_feats")
+    r = reduced.contiguous()
+    m, c = r.shape
+    arg = torch.empty((m, c), dtype=torch.int32, device=r.device)
+    check(lib.msmd_scatter_max_argmax_f32(_p(feats), n, c, _p(point2voxel.contiguous()), _p(r), m,
+                                          _p(arg), _stream()), "msmd_scatter_max_argmax_f32")
+    return arg
+
+
+def scatter_gather(voxel_feats, point2voxel):
+    """out[i] = voxel_feats[point2voxel[i]], 0 for invalid points."""
+    _need_cuda(voxel_feats, point2voxel)
+    _need_dtype(voxel_feats, torch.float32, "voxel_feats")
+    _need_dtype(point2voxel, torch.int32, "point2voxel")
+    vf = voxel_feats.contiguous()
+    m, c = vf.shape
+    n = point2voxel.shape[0]
+    out = torch.empty((n, c), dtype=torch.float32, device=vf.device)
+    check(lib.msmd_scatter_gather_f32(_p(vf), m, c, _p(point2voxel.contiguous()), n, _p(out),
+                                      _stream()), "msmd_scatter_gather_f32")
+    return out
+
+
 # ------------------------------------------------------------------ rulebooks
 def conv_output_size(in_shape, ksize, stride, padding, dilation=(1, 1, 1)):
     """mmdet3d/ops/spconv/ops.py:20-30."""

@@ -13,10 +13,12 @@ from . import kernels as K
 
 
 def voxelization(points, voxel_size, coors_range, max_points=35, max_voxels=20000):
-    """_Voxelization.forward (voxelize.py:12-59).  Dynamic voxelization
-    (max_points == -1) is not on the hot path and raises."""
+    """_Voxelization.forward (voxelize.py:12-59).  max_points == -1 or max_voxels == -1:
+    dynamic voxelization, -> coors[N, 3] (z, y, x) int32 of every point (a zero-filled
+    tensor the dynamic kernel writes, voxelize.py:41-44; out-of-range points carry -1)."""
     if max_points == -1 or max_voxels == -1:
-        raise NotImplementedError("dynamic voxelization is outside the MSMDFusion hot path")
+        with torch.no_grad():
+            return K.dynamic_voxelize(points.contiguous(), voxel_size, coors_range)
     with torch.no_grad():
         voxels, coors, num_points, _ = K.hard_voxelize(points, voxel_size, coors_range,
                                                        max_points, max_voxels)
