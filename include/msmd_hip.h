@@ -246,6 +246,34 @@ int msmd_rulebook_conv3d_fill(const int32_t* indices, int n, int batch_size,
                               void* workspace, size_t workspace_bytes,
                               msmd_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * a6t  Transposed sparse conv rulebook (SparseConvTranspose3d), same two phases
+ * replaces: sparse_conv_ext.get_indice_pairs_3d(..., transpose=1)
+ *           spconv_ops.h:108-137, geometry.h:87-140,196-245 (getValidOutPosTranspose,
+ *           getIndicePairsDeConv).
+ * Input coordinate c reaches output c*stride - padding + k (dilation 1); k is the
+ * row-major index of the offset; cells outside [0, out_shape) are dropped.  out_shape is
+ * the deconv size (in-1)*stride - 2*padding + ksize + output_padding (ops.py:33-43) and
+ * the workspace is msmd_rulebook_conv_workspace_bytes(batch_size, out_shape).  Output
+ * rows in ascending linear id; tables as msmd_rulebook_conv3d_fill's (at most one input
+ * coordinate reaches an (offset, output row); a repeated coordinate: its LAST row).
+ * ------------------------------------------------------------------------ */
+int msmd_rulebook_deconv3d_count(const int32_t* indices /* [n,4] */, int n,
+                                 int batch_size, const int* out_shape,
+                                 const int* ksize, const int* stride,
+                                 const int* padding, int32_t* n_out /* [1] */,
+                                 void* workspace, size_t workspace_bytes,
+                                 msmd_stream_t stream);
+
+int msmd_rulebook_deconv3d_fill(const int32_t* indices, int n, int batch_size,
+                                const int* out_shape, const int* ksize,
+                                const int* stride, const int* padding, int n_out,
+                                int32_t* out_indices /* [n_out,4] */,
+                                int32_t* nbr_fwd /* [K,n_out] in-row or -1 */,
+                                int32_t* nbr_bwd /* [K,n]    out-row or -1 */,
+                                void* workspace, size_t workspace_bytes,
+                                msmd_stream_t stream);
+
 /* A chain of strided convs whose input set is the previous one's output set
  * (SparseEncoder: sparse_encoder.py:175-187, only SubM convs in between): all levels
  * counted back to back -- level l+1 is marked from level l's occupancy bitmap -- so the
@@ -598,6 +626,28 @@ int msmd_bn_relu_bwd_f32(const float* x, const float* dy, int n, int c, const fl
                          const float* beta, const float* save_mean, const float* save_invstd,
                          int training, float* dx, float* dgamma, float* dbeta,
                          void* workspace, size_t workspace_bytes, msmd_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
+ * a6p  Sparse max-pool (SparseMaxPool3d), fp32, any channel count
+ * replaces: sparse_conv_ext.indice_maxpool_fp32 / indice_maxpool_backward_fp32
+ *           (pool_ops.h:34,71; functors src/maxpool.cc:20-62)
+ * Over the pool's rulebook (the strided conv rulebook of the same geometry), read
+ * input-stationary through nbr_bwd[K, n_in] (output row or -1), which lists every
+ * pair, repeated input coordinates included.
+ * fwd: out [n_out,C] is zeroed here; an input value replaces the output only when
+ *      out < in -- an all-negative window gives 0, a NaN never wins.  Exact.
+ * bwd: din [n_in,C] = sum over k ascending of dout[o] where out[o] == in[i]; every
+ *      element written once, no float atomics (the functor's order: bitwise equal).
+ * ------------------------------------------------------------------------ */
+int msmd_sparse_maxpool_fwd_f32(const float* in /* [n_in,C] */, int n_in, int num_channels,
+                                const int32_t* nbr_bwd /* [K,n_in] */, int kvol, int n_out,
+                                float* out /* [n_out,C] */, msmd_stream_t stream);
+int msmd_sparse_maxpool_bwd_f32(const float* in /* [n_in,C] */,
+                                const float* out /* [n_out,C] */,
+                                const float* dout /* [n_out,C] */, int n_in,
+                                int num_channels, const int32_t* nbr_bwd, int kvol,
+                                int n_out, float* din /* [n_in,C] */,
+                                msmd_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
  * a12  SparseConvTensor.dense(): BEV scatter

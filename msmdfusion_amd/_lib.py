@@ -65,6 +65,11 @@ SIGNATURES = {
                                                 _sz, _vp]),
     "msmd_rulebook_conv3d_count": (_i, [_vp, _i, _i, _ip, _ip, _ip, _ip, _vp, _vp, _sz, _vp]),
     "msmd_rulebook_conv3d_fill": (_i, [_vp, _i, _i, _ip, _ip, _ip, _ip, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "msmd_rulebook_deconv3d_count": (_i, [_vp, _i, _i, _ip, _ip, _ip, _ip, _vp, _vp, _sz, _vp]),
+    "msmd_rulebook_deconv3d_fill": (_i, [_vp, _i, _i, _ip, _ip, _ip, _ip, _i, _vp, _vp, _vp, _vp, _sz,
+                                         _vp]),
+    "msmd_sparse_maxpool_fwd_f32": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "msmd_sparse_maxpool_bwd_f32": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp]),
     "msmd_rulebook_pairs_workspace_bytes": (_sz, [_i, _i]),
     "msmd_rulebook_pairs": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
     "msmd_spconv_packed_weight_elems": (_sz, [_i, _i, _i]),

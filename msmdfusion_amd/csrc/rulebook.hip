@@ -348,6 +348,26 @@ __device__ __forceinline__ bool out_coord(int c, int kc, int pad, int stride, in
   return true;
 }
 
+// Transposed conv (geometry.h:87-140, getValidOutPosTranspose, dilation 1): input coordinate c
+// reaches val = c * stride - pad + kc through offset component kc, kept when inside the grid.
+__device__ __forceinline__ bool deconv_coord(int c, int kc, int pad, int stride, int lim,
+                                             int* val) {
+  int t = c * stride - pad + kc;
+  if (t < 0 || t >= lim) return false;
+  *val = t;
+  return true;
+}
+
+template <bool kTransposed>
+__device__ __forceinline__ bool reach(int c, int kc, int pad, int stride, int lim, int* val) {
+  return kTransposed ? deconv_coord(c, kc, pad, stride, lim, val)
+                     : out_coord(c, kc, pad, stride, lim, val);
+}
+
+// kTransposed: the same marking / filling passes over the transposed geometry -- output rows
+// in ascending linear id, one input row per (offset, output row) (at most one input coordinate
+// reaches it), nbr_bwd complete.
+template <bool kTransposed = false>
 __global__ __launch_bounds__(256) void conv_mark(const int32_t* __restrict__ idx, int n, Geom g,
                                                  uint32_t* bits) {
   int i = blockIdx.x * 256 + threadIdx.x;
@@ -356,9 +376,9 @@ __global__ __launch_bounds__(256) void conv_mark(const int32_t* __restrict__ idx
   const int kx = k % g.ks[2], ky = (k / g.ks[2]) % g.ks[1], kz = k / (g.ks[2] * g.ks[1]);
   int4 r = ((const int4*)idx)[i];
   int z, y, x;
-  if (out_coord(r.y, kz, g.pd[0], g.st[0], g.shape[0], &z) &&
-      out_coord(r.z, ky, g.pd[1], g.st[1], g.shape[1], &y) &&
-      out_coord(r.w, kx, g.pd[2], g.st[2], g.shape[2], &x))
+  if (reach<kTransposed>(r.y, kz, g.pd[0], g.st[0], g.shape[0], &z) &&
+      reach<kTransposed>(r.z, ky, g.pd[1], g.st[1], g.shape[1], &y) &&
+      reach<kTransposed>(r.w, kx, g.pd[2], g.st[2], g.shape[2], &x))
     bitmap_set(bits, cell_id(r.x, z, y, x, g.shape));
 }
 
@@ -445,6 +465,7 @@ __global__ __launch_bounds__(256) void conv_mark_gather(const uint32_t* __restri
   if (lane == 32 && w0 + 1 < words) out_bits[w0 + 1] = (uint32_t)(m >> 32);
 }
 
+template <bool kTransposed = false>
 __global__ __launch_bounds__(256) void conv_fill(const int32_t* __restrict__ idx, int n, Geom g,
                                                  const uint32_t* __restrict__ bits,
                                                  const int* __restrict__ prefix, int n_out,
@@ -457,9 +478,9 @@ __global__ __launch_bounds__(256) void conv_fill(const int32_t* __restrict__ idx
   const int kx = k % g.ks[2], ky = (k / g.ks[2]) % g.ks[1], kz = k / (g.ks[2] * g.ks[1]);
   int4 r = ((const int4*)idx)[i];
   int z, y, x, o = -1;
-  if (out_coord(r.y, kz, g.pd[0], g.st[0], g.shape[0], &z) &&
-      out_coord(r.z, ky, g.pd[1], g.st[1], g.shape[1], &y) &&
-      out_coord(r.w, kx, g.pd[2], g.st[2], g.shape[2], &x)) {
+  if (reach<kTransposed>(r.y, kz, g.pd[0], g.st[0], g.shape[0], &z) &&
+      reach<kTransposed>(r.z, ky, g.pd[1], g.st[1], g.shape[1], &y) &&
+      reach<kTransposed>(r.w, kx, g.pd[2], g.st[2], g.shape[2], &x)) {
     o = bitmap_rank(bits, prefix, cell_id(r.x, z, y, x, g.shape));
     if (o < n_out) {
       // (k,o) has exactly one source COORDINATE; when the input set repeats a coordinate
@@ -986,7 +1007,7 @@ MSMD_EXPORT int msmd_rulebook_conv3d_count(const int32_t* indices, int n, int ba
   hipStream_t st = (hipStream_t)stream;
   hipMemsetAsync(w.bits, 0, sizeof(uint32_t) * w.words, st);
   if (n > 0)
-    MSMD_LAUNCH(conv_mark, dim3(ceil_div(n, 256), g.kvol), dim3(256), 0, st, indices, n, g,
+    MSMD_LAUNCH(conv_mark<false>, dim3(ceil_div(n, 256), g.kvol), dim3(256), 0, st, indices, n, g,
                        w.bits);
   device_scan(PopcCount{w.bits}, StorePrefix{w.prefix}, (int)w.words, w.tiles, n_out, -1, st);
   return launch_status();
@@ -1036,7 +1057,7 @@ MSMD_EXPORT int msmd_rulebook_conv3d_count_chain(const int32_t* indices, int n, 
     hipMemsetAsync(w.bits, 0, sizeof(uint32_t) * w.words, st);
     if (l == 0) {
       if (n > 0)
-        MSMD_LAUNCH(conv_mark, dim3(ceil_div(n, 256), g.kvol), dim3(256), 0, st, indices, n, g,
+        MSMD_LAUNCH(conv_mark<false>, dim3(ceil_div(n, 256), g.kvol), dim3(256), 0, st, indices, n, g,
                     w.bits);
     } else {
       const long oc = (long)batch_size * g.shape[0] * g.shape[1] * g.shape[2];
@@ -1076,8 +1097,59 @@ MSMD_EXPORT int msmd_rulebook_conv3d_fill(const int32_t* indices, int n, int bat
   hipStream_t st = (hipStream_t)stream;
   if (n_out > 0) hipMemsetAsync(nbr_fwd, 0xFF, sizeof(int32_t) * (size_t)g.kvol * n_out, st);
   if (n > 0)
-    MSMD_LAUNCH(conv_fill, dim3(ceil_div(n, 256), g.kvol), dim3(256), 0, st, indices, n, g,
+    MSMD_LAUNCH(conv_fill<false>, dim3(ceil_div(n, 256), g.kvol), dim3(256), 0, st, indices, n, g,
                        w.bits, w.prefix, n_out, out_indices, nbr_fwd, nbr_bwd);
+  return launch_status();
+}
+
+// ------------------------------------------------------------- transposed ---
+// getIndicePairsDeConv (geometry.h:196-245) on the strided builder's bitmap + rank scheme: the
+// output grid is the deconv size, (in - 1) * s - 2p + k + output_padding (ops.py:33-43), which
+// the caller passes as out_shape; the workspace is msmd_rulebook_conv_workspace_bytes of it.
+MSMD_EXPORT int msmd_rulebook_deconv3d_count(const int32_t* indices, int n, int batch_size,
+                                             const int* out_shape, const int* ksize,
+                                             const int* stride, const int* padding,
+                                             int32_t* n_out, void* workspace,
+                                             size_t workspace_bytes, msmd_stream_t stream) {
+  Geom g;
+  if (!stride || !padding || !n_out) return MSMD_ERR_INVALID_ARG;
+  int rc = check_geom(out_shape, ksize, stride, padding, batch_size, &g);
+  if (rc) return rc;
+  if (n < 0 || (n > 0 && !indices)) return MSMD_ERR_INVALID_ARG;
+  Arena a(workspace, workspace_bytes);
+  ConvWs w;
+  carve_conv(a, &w, batch_size, out_shape);
+  if (!a.ok()) return MSMD_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  hipMemsetAsync(w.bits, 0, sizeof(uint32_t) * w.words, st);
+  if (n > 0)
+    MSMD_LAUNCH(conv_mark<true>, dim3(ceil_div(n, 256), g.kvol), dim3(256), 0, st, indices, n, g,
+                w.bits);
+  device_scan(PopcCount{w.bits}, StorePrefix{w.prefix}, (int)w.words, w.tiles, n_out, -1, st);
+  return launch_status();
+}
+
+MSMD_EXPORT int msmd_rulebook_deconv3d_fill(const int32_t* indices, int n, int batch_size,
+                                            const int* out_shape, const int* ksize,
+                                            const int* stride, const int* padding, int n_out,
+                                            int32_t* out_indices, int32_t* nbr_fwd,
+                                            int32_t* nbr_bwd, void* workspace,
+                                            size_t workspace_bytes, msmd_stream_t stream) {
+  Geom g;
+  if (!stride || !padding) return MSMD_ERR_INVALID_ARG;
+  int rc = check_geom(out_shape, ksize, stride, padding, batch_size, &g);
+  if (rc) return rc;
+  if (n < 0 || n_out < 0 || (n_out > 0 && (!out_indices || !nbr_fwd)))
+    return MSMD_ERR_INVALID_ARG;
+  Arena a(workspace, workspace_bytes);
+  ConvWs w;
+  carve_conv(a, &w, batch_size, out_shape);
+  if (!a.ok()) return MSMD_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  if (n_out > 0) hipMemsetAsync(nbr_fwd, 0xFF, sizeof(int32_t) * (size_t)g.kvol * n_out, st);
+  if (n > 0)
+    MSMD_LAUNCH(conv_fill<true>, dim3(ceil_div(n, 256), g.kvol), dim3(256), 0, st, indices, n, g,
+                w.bits, w.prefix, n_out, out_indices, nbr_fwd, nbr_bwd);
   return launch_status();
 }
 
@@ -1175,7 +1247,7 @@ MSMD_EXPORT int msmd_rulebook_add_conv_count_chain(const int32_t* const* extra, 
     hipMemsetAsync(w.bits, 0, sizeof(uint32_t) * w.words, st);
     if (l == 0) {
       if (n_extra[0] > 0)
-        MSMD_LAUNCH(conv_mark, dim3(ceil_div(n_extra[0], 256), g.kvol), dim3(256), 0, st, extra[0],
+        MSMD_LAUNCH(conv_mark<false>, dim3(ceil_div(n_extra[0], 256), g.kvol), dim3(256), 0, st, extra[0],
                     n_extra[0], g, w.bits);
     } else {
       const long oc = (long)batch_size * g.shape[0] * g.shape[1] * g.shape[2];

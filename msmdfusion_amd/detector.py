@@ -29,6 +29,7 @@ from torch import nn
 
 from . import spconv
 from .fusion import SparseFusionPath
+from . import sparse_unet  # noqa: F401,E402  (registers SparseUNet in MIDDLE_ENCODERS)
 from .registry import (DETECTORS, build_backbone, build_middle_encoder, build_neck,
                        build_voxel_encoder)
 from .voxelize import Voxelization

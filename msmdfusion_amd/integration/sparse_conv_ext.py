@@ -1,7 +1,11 @@
 """`sparse_conv_ext` -- the pybind module of mmdet3d/ops/spconv (src/all.cc:21-51), on
 the C ABI: the three functions mmdet3d/ops/spconv/ops.py:48-137 and functional.py:20-75
-call for a 3-D SubMConv3d / SparseConv3d.  2-D / 4-D, transposed, pooling, fused-BN and
-half variants are outside the hot path and raise.
+call for a 3-D SubMConv3d / SparseConv3d, plus the transposed rulebook
+(get_indice_pairs_3d(..., transpose=1)) and inverse convs (indice_conv_fp32 /
+indice_conv_backward_fp32 with inverse=1).  2-D / 4-D, fused-BN and half variants raise, and
+so do indice_maxpool_fp32 / indice_maxpool_backward_fp32: sparse max-pooling is reached through
+spconv.SparseMaxPool3d and kernels.maxpool_fwd / maxpool_bwd (over the library's own
+input-side table, which lists every pair), not through pair lists.
 
 Formats are the reference's (spconv_ops.h:55-59): `indicePairs` int32 [K,2,N] padded
 with -1 ([k][0] input rows, [k][1] output rows), `indiceNum` int32 [K]; strided-conv
@@ -38,9 +42,11 @@ def _tables_from_pairs(indice_pairs, indice_num, n_in, n_out):
 
 def get_indice_pairs_3d(indices, batch, outShape, spatialShape, ksize, stride, padding, dilation,
                         outPadding, subM, transpose):
-    """spconv::getIndicePair<3> (spconv_ops.h:33-140) -> [outIds, indicePairs, indiceNum]."""
-    if transpose:
-        raise RuntimeError("get_indice_pairs_3d: transposed convolutions are not built")
+    """spconv::getIndicePair<3> (spconv_ops.h:33-140) -> [outIds, indicePairs, indiceNum].
+    transpose=1: the transposed geometry (getIndicePairsDeConv); outShape must be its deconv
+    size (ops.get_deconv_output_size)."""
+    if transpose and subM:
+        raise RuntimeError("get_indice_pairs_3d: a SubM rulebook cannot be transposed")
     if any(int(d) != 1 for d in dilation):
         raise RuntimeError("get_indice_pairs_3d: only dilation 1 is built")
     if indices.dim() != 2 or indices.shape[1] != 4 or indices.dtype != torch.int32:
@@ -53,8 +59,17 @@ def get_indice_pairs_3d(indices, batch, outShape, spatialShape, ksize, stride, p
             _TABLES[pairs.data_ptr()] = (pairs, nbr, nbr, True)
             _trim()
             return [indices, pairs, num]
-        out_ids, nbr_fwd, nbr_bwd, out_shape = K.rulebook_conv(indices, batch, spatialShape, ksize,
-                                                               stride, padding)
+        if transpose:
+            want = K.deconv_output_size(spatialShape, ksize, stride, padding, outPadding)
+            if [int(x) for x in outShape] != want:
+                raise RuntimeError("get_indice_pairs_3d: outShape %s does not match the transposed "
+                                   "convolution geometry (%s)" % (list(outShape), want))
+            out_ids, nbr_fwd, nbr_bwd, out_shape = K.rulebook_deconv(indices, batch, spatialShape,
+                                                                     ksize, stride, padding,
+                                                                     outPadding)
+        else:
+            out_ids, nbr_fwd, nbr_bwd, out_shape = K.rulebook_conv(indices, batch, spatialShape,
+                                                                   ksize, stride, padding)
         if [int(x) for x in outShape] != [int(x) for x in out_shape]:
             raise RuntimeError("get_indice_pairs_3d: outShape %s does not match the convolution "
                                "geometry (%s)" % (list(outShape), list(out_shape)))
@@ -76,26 +91,41 @@ def _kio(filters):
 
 
 def indice_conv_fp32(features, filters, indicePairs, indiceNum, numActOut, inverse, subM):
-    """spconv::indiceConv<float> (spconv_ops.h:260-361) -> output features [numActOut,Cout]."""
-    if inverse:
-        raise RuntimeError("indice_conv_fp32: inverse convolutions are not built")
+    """spconv::indiceConv<float> (spconv_ops.h:260-361) -> output features [numActOut,Cout].
+    inverse=1: the pairs read the other way round (features are the rulebook's output rows,
+    the result its input rows): the rulebook's input-side table is the forward table."""
+    if inverse and subM:
+        raise RuntimeError("indice_conv_fp32: a SubM rulebook has no inverse")
     w = _kio(filters)
     with torch.cuda.device(features.device):
-        fwd, _, _ = _tables_from_pairs(indicePairs, indiceNum, features.shape[0], int(numActOut))
-        return K.conv_forward(features, K.pack_weight(w), fwd, int(numActOut), w.shape[2])
+        if inverse:
+            _, table, _ = _tables_from_pairs(indicePairs, indiceNum, int(numActOut),
+                                             features.shape[0])
+        else:
+            table, _, _ = _tables_from_pairs(indicePairs, indiceNum, features.shape[0],
+                                             int(numActOut))
+        return K.conv_forward(features, K.pack_weight(w), table, int(numActOut), w.shape[2])
 
 
 def indice_conv_backward_fp32(features, filters, outGrad, indicePairs, indiceNum, inverse, subM):
-    """spconv::indiceConvBackward<float> (spconv_ops.h:363-456) -> [inputGrad, filtersGrad]."""
-    if inverse:
-        raise RuntimeError("indice_conv_backward_fp32: inverse convolutions are not built")
+    """spconv::indiceConvBackward<float> (spconv_ops.h:363-456) -> [inputGrad, filtersGrad].
+    inverse=1: the inverse conv's gradients (the rulebook's forward table carries dgrad, the
+    pair lists swapped carry wgrad).  The dgrad of an inverse conv whose couple had repeated
+    input coordinates reaches only the last row of each (the forward table keeps one)."""
+    if inverse and subM:
+        raise RuntimeError("indice_conv_backward_fp32: a SubM rulebook has no inverse")
     w = _kio(filters)
     n_in = features.shape[0]
     with torch.cuda.device(features.device):
-        _, bwd, flip = _tables_from_pairs(indicePairs, indiceNum, n_in, outGrad.shape[0])
-        d_in = K.conv_forward(outGrad, K.pack_weight(w, transpose=True), bwd, n_in, w.shape[1],
+        if inverse:
+            table, _, flip = _tables_from_pairs(indicePairs, indiceNum, outGrad.shape[0], n_in)
+            pairs = indicePairs.flip(1).contiguous()
+        else:
+            _, table, flip = _tables_from_pairs(indicePairs, indiceNum, n_in, outGrad.shape[0])
+            pairs = indicePairs.contiguous()
+        d_in = K.conv_forward(outGrad, K.pack_weight(w, transpose=True), table, n_in, w.shape[1],
                               weight_flip=flip)
-        d_w = K.conv_wgrad(features, outGrad, indicePairs.contiguous(), indiceNum)
+        d_w = K.conv_wgrad(features, outGrad, pairs, indiceNum)
         return [d_in, d_w.view(filters.shape)]
 
 

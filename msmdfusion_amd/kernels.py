@@ -613,6 +613,49 @@ def rulebook_conv_chain(indices, batch_size, spatial_shape, geoms, need_bwd=True
     return out
 
 
+def deconv_output_size(in_shape, ksize, stride, padding, output_padding=(0, 0, 0),
+                       dilation=(1, 1, 1)):
+    """mmdet3d/ops/spconv/ops.py:33-43: (in - 1) * s - 2p + k + output_padding (the
+    reference's formula: dilation does not enter it)."""
+    ks, st, pd, op = _expand3(ksize), _expand3(stride), _expand3(padding), _expand3(output_padding)
+    for k in ks:
+        if k == -1:
+            raise ValueError("deconv don't support kernel_size < 0")
+    return [(int(in_shape[i]) - 1) * st[i] - 2 * pd[i] + ks[i] + op[i] for i in range(3)]
+
+
+def rulebook_deconv(indices, batch_size, spatial_shape, ksize, stride, padding,
+                    output_padding=(0, 0, 0), need_bwd=True):
+    """Transposed-conv rulebook (geometry.h:196-245): input c reaches c*s - p + k.
+    -> (out_indices[M,4] in ascending linear id, nbr_fwd[K,M], nbr_bwd[K,N] | None, out_shape);
+    one host read (the output count)."""
+    _need_bzyx(indices)
+    _need_cuda(indices)
+    idx = indices.contiguous().int()
+    n = idx.shape[0]
+    dev = idx.device
+    ks, st, pd = _expand3(ksize), _expand3(stride), _expand3(padding)
+    out_shape = deconv_output_size(list(spatial_shape), ks, st, pd, output_padding)
+    if any(s < 1 for s in out_shape):
+        raise ValueError("transposed conv output shape %s is empty" % (out_shape,))
+    kvol = kernel_volume(ks)
+    nbytes = lib.msmd_rulebook_conv_workspace_bytes(int(batch_size), int3(out_shape))
+    ws = _ws(nbytes, dev)
+    count = _Count(dev)
+    check(lib.msmd_rulebook_deconv3d_count(_p(idx), n, int(batch_size), int3(out_shape),
+                                           int3(ks), int3(st), int3(pd), count.ptr, _p(ws),
+                                           nbytes, _stream()), "msmd_rulebook_deconv3d_count")
+    m = count.read()
+    out_idx = torch.empty((m, 4), dtype=torch.int32, device=dev)
+    nbr_fwd = torch.empty((kvol, m), dtype=torch.int32, device=dev)
+    nbr_bwd = torch.empty((kvol, n), dtype=torch.int32, device=dev) if need_bwd else None
+    check(lib.msmd_rulebook_deconv3d_fill(_p(idx), n, int(batch_size), int3(out_shape), int3(ks),
+                                          int3(st), int3(pd), m, _p(out_idx), _p(nbr_fwd),
+                                          _p(nbr_bwd), _p(ws), nbytes, _stream()),
+          "msmd_rulebook_deconv3d_fill")
+    return out_idx, nbr_fwd, nbr_bwd, out_shape
+
+
 def rulebook_pairs(nbr, ld=None):
     """nbr[K,M] -> (indice_pairs[K,2,ld], indice_num[K]): the reference's
     rulebook format (spconv_ops.h:55-59), pairs sorted by output row."""
@@ -627,6 +670,51 @@ def rulebook_pairs(nbr, ld=None):
     check(lib.msmd_rulebook_pairs(_p(nbr.contiguous()), kvol, m, _p(pairs), ld, _p(num), _p(ws),
                                   nbytes, _stream()), "msmd_rulebook_pairs")
     return pairs, num
+
+
+# ------------------------------------------------------------------ max-pool
+def _need_pool_args(feat, nbr_bwd):
+    _need_cuda(feat, nbr_bwd)
+    _need_dtype(feat, torch.float32, "features")
+    _need_dtype(nbr_bwd, torch.int32, "nbr_bwd")
+    if feat.dim() != 2 or nbr_bwd.dim() != 2 or nbr_bwd.shape[1] != feat.shape[0]:
+        raise ValueError("max-pool: features [N,C] and nbr_bwd [K,N] expected, got %s and %s"
+                         % (tuple(feat.shape), tuple(nbr_bwd.shape)))
+    if feat.shape[1] < 1:
+        raise ValueError("max-pool: at least one channel")
+
+
+def maxpool_fwd(feat, nbr_bwd, n_out):
+    """Sparse max-pool over a strided rulebook's input-side table nbr_bwd[K, N] (every pair
+    listed): out[o] starts at 0 and takes in[i] where out < in (maxpool.cc:20-40).
+    -> [n_out, C]."""
+    _need_pool_args(feat, nbr_bwd)
+    feat, nbr_bwd = feat.contiguous(), nbr_bwd.contiguous()
+    n, c = feat.shape
+    out = torch.empty((int(n_out), c), dtype=torch.float32, device=feat.device)
+    check(lib.msmd_sparse_maxpool_fwd_f32(_p(feat), n, c, _p(nbr_bwd), nbr_bwd.shape[0],
+                                          int(n_out), _p(out), _stream()),
+          "msmd_sparse_maxpool_fwd_f32")
+    return out
+
+
+def maxpool_bwd(feat, out, grad_out, nbr_bwd):
+    """din[i] = sum over k ascending of dout[o] where out[o] == in[i] (maxpool.cc:42-62).
+    -> [N, C], bitwise the functor's loop."""
+    _need_pool_args(feat, nbr_bwd)
+    _need_cuda(out, grad_out)
+    _need_dtype(out, torch.float32, "out")
+    _need_dtype(grad_out, torch.float32, "grad_out")
+    n, c = feat.shape
+    if out.shape != grad_out.shape or (out.dim() == 2 and out.shape[1] != c):
+        raise ValueError("max-pool backward: out / grad_out must both be [n_out, %d]" % c)
+    feat, out, grad_out = feat.contiguous(), out.contiguous(), grad_out.contiguous()
+    din = torch.empty_like(feat)
+    check(lib.msmd_sparse_maxpool_bwd_f32(_p(feat), _p(out), _p(grad_out), n, c,
+                                          _p(nbr_bwd.contiguous()), nbr_bwd.shape[0],
+                                          out.shape[0], _p(din), _stream()),
+          "msmd_sparse_maxpool_bwd_f32")
+    return din
 
 
 # ------------------------------------------------------------------ convolution

@@ -61,15 +61,20 @@ def make_sparse_convmodule(in_channels, out_channels, kernel_size, indice_key, s
                            padding=0, conv_type="SubMConv3d", norm_cfg=None,
                            order=("conv", "norm", "act")):
     """sparse_block.py:129-191: SparseSequential(conv, BN1d, ReLU) -- children
-    named '0','1','2'."""
+    named '0','1','2'.  Inverse convs take neither stride nor padding (their geometry is the
+    couple conv's)."""
     assert isinstance(order, tuple) and len(order) <= 3
     assert set(order) | {"conv", "norm", "act"} == {"conv", "norm", "act"}
     conv_cfg = dict(type=conv_type, indice_key=indice_key)
     layers = []
     for layer in order:
         if layer == "conv":
-            layers.append(build_conv_layer(conv_cfg, in_channels, out_channels, kernel_size,
-                                           stride=stride, padding=padding, bias=False))
+            if conv_type in ("SparseInverseConv3d", "SparseInverseConv2d", "SparseInverseConv1d"):
+                layers.append(build_conv_layer(conv_cfg, in_channels, out_channels, kernel_size,
+                                               bias=False))
+            else:
+                layers.append(build_conv_layer(conv_cfg, in_channels, out_channels, kernel_size,
+                                               stride=stride, padding=padding, bias=False))
         elif layer == "norm":
             layers.append(build_norm_layer(norm_cfg, out_channels)[1])
         elif layer == "act":

@@ -6,8 +6,10 @@ Kept: constructor signature and defaults (bug_fix/conv.py:46-64,873-885), KRSC
 weight layout [Cout, kd, kh, kw, Cin] of the GPU build (:114-117) so published
 checkpoints load, kaiming-uniform init with a=sqrt(5) over fan_in = Cin*K
 (:163-183), output shape rule (:196-204), indice_key reuse for SubM only
-(:364-375), bias add (:448-449).  Transposed / inverse convs and groups are
-outside the hot path and raise.
+(:364-375), bias add (:448-449).  Transposed convs (SparseConvTranspose3d) build
+their own rulebook (kernels.rulebook_deconv); inverse convs (SparseInverseConv3d,
+:350-362) run over the couple conv's rulebook read the other way round
+(IndiceData.inverted).  Groups and other ranks than 3 raise.
 """
 import math
 from typing import List, Optional, Tuple, Union
@@ -55,8 +57,10 @@ class SparseConvolution(SparseModule):
         assert groups == 1, "don't support groups for now"
         if ndim != 3:
             raise NotImplementedError("the MSMDFusion hot path is 3-D only")
-        if transposed or inverse:
-            raise NotImplementedError("transposed / inverse sparse convs are outside the hot path")
+        if subm and (transposed or inverse):
+            raise ValueError("a SubM conv cannot be transposed or inverse")
+        if transposed and inverse:
+            raise ValueError("a conv is transposed or inverse, not both")
         self.ndim = ndim
         self.in_channels = in_channels
         self.out_channels = out_channels
@@ -66,6 +70,8 @@ class SparseConvolution(SparseModule):
         self.padding = expand_nd(ndim, padding)
         kv = int(np.prod(self.kernel_size))
         self.conv1x1 = kv == 1
+        if inverse:     # (the output set is the couple's input set, never the input's own)
+            self.conv1x1 = False
         if not subm:
             self.conv1x1 &= int(np.prod(self.stride)) == 1
             if self.conv1x1:
@@ -135,11 +141,14 @@ class SparseConvolution(SparseModule):
         assert input.features.shape[1] == self.in_channels, "channel size mismatch"
         features = input.features
         spatial_shape = input.spatial_shape
-        if not self.subm:
+        if self.subm or self.inverse:   # (inverse: the couple's input shape, set below)
+            out_spatial_shape = spatial_shape
+        elif self.transposed:
+            out_spatial_shape = K.deconv_output_size(spatial_shape, self.kernel_size, self.stride,
+                                                     self.padding, self.output_padding)
+        else:
             out_spatial_shape = K.conv_output_size(spatial_shape, self.kernel_size, self.stride,
                                                    self.padding, self.dilation)
-        else:
-            out_spatial_shape = spatial_shape
         out_tensor = input.shadow_copy()
         if self.conv1x1:
             kio = self.weight_kio()[0]
@@ -153,11 +162,26 @@ class SparseConvolution(SparseModule):
         datas = input.find_indice_pair(self.indice_key)
         if datas is not None:
             assert isinstance(datas, IndiceData)
+        if self.inverse:
+            # bug_fix/conv.py:350-362: the couple's pairs the other way round; the output rows
+            # are the couple's input index tensor itself (later SubM indice_key checks pass)
+            assert datas is not None and self.indice_key is not None
+            assert datas.is_subm is False, \
+                "inverse conv can only be used with standard conv and pool ops."
+            out_spatial_shape = list(datas.spatial_shape)
+            assert datas.ksize == self.kernel_size, \
+                "inverse conv must have same kernel size as its couple conv"
+            if input.indices.shape[0] != datas.n_out:
+                raise ValueError(f"inverse conv: the input has {input.indices.shape[0]} voxels, "
+                                 f"its couple's output set {datas.n_out}")
+            datas = datas.inverted()
+        elif datas is not None:
             assert self.subm, "only support reuse subm indices"
             self._check_subm_reuse_valid(input, spatial_shape, datas)
         else:
             datas = input.cached_rulebook(self.kernel_size, self.stride, self.padding,
-                                          self.dilation, self.subm)
+                                          self.dilation, self.subm, transposed=self.transposed,
+                                          output_padding=self.output_padding)
             if self.indice_key is not None:
                 msg = f"your indice key {self.indice_key} already exists in this sparse tensor."
                 assert self.indice_key not in indice_dict, msg
@@ -204,6 +228,23 @@ class SparseConv3d(SparseConvolution):
         super().__init__(3, in_channels, out_channels, kernel_size, stride, padding, dilation,
                          groups, bias, indice_key=indice_key, algo=algo, fp32_accum=fp32_accum,
                          name=name)
+
+
+@CONV_LAYERS.register_module()
+class SparseConvTranspose3d(SparseConvolution):
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1,
+                 groups=1, bias=True, indice_key=None, algo=None, fp32_accum=None, name=None):
+        super().__init__(3, in_channels, out_channels, kernel_size, stride, padding, dilation,
+                         groups, bias, transposed=True, indice_key=indice_key, algo=algo,
+                         fp32_accum=fp32_accum, name=name)
+
+
+@CONV_LAYERS.register_module()
+class SparseInverseConv3d(SparseConvolution):
+    def __init__(self, in_channels, out_channels, kernel_size, indice_key, bias=True, algo=None,
+                 fp32_accum=None, name=None):
+        super().__init__(3, in_channels, out_channels, kernel_size, bias=bias, inverse=True,
+                         indice_key=indice_key, algo=algo, fp32_accum=fp32_accum, name=name)
 
 
 @CONV_LAYERS.register_module()

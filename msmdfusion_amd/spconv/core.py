@@ -154,6 +154,24 @@ class IndiceData:
         self._tiled_bwd = None
         self._prefix_fwd = {}
         self._prefix_bwd = {}
+        self._inverted = None
+
+    def inverted(self):
+        """The rulebook of the inverse conv paired with this one (bug_fix/conv.py:350-362): the
+        same pairs read the other way round -- the tables swapped (nbr_bwd is complete, so the
+        inverse's forward and weight-gradient pairs are all there), input and output index sets
+        and shapes swapped.  Tiling, order, prefix and pair caches of its own; built once."""
+        if self.is_subm:
+            raise RuntimeError("inverse conv can only be used with standard conv and pool ops.")
+        if self.nbr_bwd is None:
+            raise RuntimeError("this rulebook was built without its input-side table (nbr_bwd): "
+                               "an inverse conv cannot use it")
+        if self._inverted is None:
+            self._inverted = IndiceData(self.indices, self.out_indices, self.nbr_bwd, self.nbr_fwd,
+                                        False, list(self.out_spatial_shape),
+                                        list(self.spatial_shape), self.ksize, self.stride,
+                                        self.padding, self.dilation, self.algo)
+        return self._inverted
 
     def check_ready(self):
         """Raise if the table cannot be read yet / any more (deferred fill still pending, or
@@ -330,9 +348,16 @@ class IndiceData:
 
 
 def build_rulebook(indices, batch_size, spatial_shape, ksize, stride, padding, dilation, subm,
-                   algo=None):
+                   algo=None, transposed=False, output_padding=(0, 0, 0)):
     if any(d != 1 for d in dilation):
         raise NotImplementedError("only dilation 1 is built (all reference configs use it)")
+    if transposed:
+        if subm:
+            raise ValueError("a SubM conv cannot be transposed")
+        out_idx, nbr_fwd, nbr_bwd, out_shape = K.rulebook_deconv(
+            indices, batch_size, spatial_shape, ksize, stride, padding, output_padding)
+        return IndiceData(out_idx, indices, nbr_fwd, nbr_bwd, False, list(spatial_shape),
+                          list(out_shape), ksize, stride, padding, dilation, algo)
     if subm:
         if any(k % 2 == 0 for k in ksize):
             raise NotImplementedError("SubM needs odd kernel sizes")
@@ -356,6 +381,13 @@ def build_rulebook(indices, batch_size, spatial_shape, ksize, stride, padding, d
                                                            ksize, stride, padding)
     return IndiceData(out_idx, indices, nbr_fwd, nbr_bwd, False, list(spatial_shape),
                       list(out_shape), ksize, stride, padding, dilation, algo)
+
+
+def _changes_set_otherwise(layer):
+    """A transposed or inverse conv or a pool: a layer that changes the voxel set other than
+    as a strided conv does."""
+    return bool(getattr(layer, "transposed", False) or getattr(layer, "inverse", False)
+                or getattr(layer, "is_pool", False))
 
 
 class SparseConvTensor:
@@ -424,19 +456,23 @@ class SparseConvTensor:
             return None
         return self.indice_dict.get(key)
 
-    def cached_rulebook(self, ksize, stride, padding, dilation, subm):
+    def cached_rulebook(self, ksize, stride, padding, dilation, subm, transposed=False,
+                        output_padding=(0, 0, 0)):
         # after voxel_modality_split the tensors carry 5-column indices
         # (b,mix,z,y,x: MSMDFusion.py:322-323); spconv asserts on ndim there too
         assert self.indices.shape[1] == 4, \
             f"sparse conv needs (b,z,y,x) indices, got {self.indices.shape[1]} columns"
         ident = (self.indices.data_ptr(), self.indices.shape[0], tuple(self.spatial_shape),
                  tuple(ksize), tuple(stride), tuple(padding), tuple(dilation), bool(subm))
+        if transposed:      # (the keys of the other geometries stay as seed_strided_chain writes them)
+            ident += ("transposed", tuple(int(v) for v in K._expand3(output_padding)))
         hit = self._rb_cache.get(ident)
         # (an entry whose deferred fill failed is rebuilt, not handed out again)
         if hit is not None and hit.indices is self.indices and hit.nbr_fwd is not None:
             return hit
         rb = build_rulebook(self.indices, self.batch_size, self.spatial_shape, list(ksize),
-                            list(stride), list(padding), list(dilation), subm)
+                            list(stride), list(padding), list(dilation), subm,
+                            transposed=transposed, output_padding=K._expand3(output_padding))
         self._rb_cache[ident] = rb
         return rb
 
@@ -446,8 +482,15 @@ class SparseConvTensor:
         previous one's output set, and all their output sets can be counted on the device
         back to back with a single host read (kernels.rulebook_conv_chain) instead of one
         read per conv.  The rulebooks land in the shared cache under the keys plan() /
-        forward() will look up; results are those of the level-by-level path."""
-        strided = [c for c in convs if not c.subm and not getattr(c, "conv1x1", False)]
+        forward() will look up; results are those of the level-by-level path.  The chain ends
+        at the first layer that changes the voxel set otherwise (a transposed or inverse conv,
+        a pool): those are left to plan()."""
+        strided = []
+        for c in convs:
+            if _changes_set_otherwise(c):
+                break
+            if not c.subm and not getattr(c, "conv1x1", False):
+                strided.append(c)
         if len(strided) < 2 or os.environ.get("MSMD_CONV_CHAIN", "1") != "1" or \
                 any(d != 1 for c in strided for d in c.dilation):
             return
@@ -465,24 +508,43 @@ class SparseConvTensor:
 
     def plan(self, convs, need_grad, strided_outputs=None):
         """Index-only pre-pass: build (or fetch) the rulebook of every sparse
-        conv in `convs` (execution order), following the voxel set through the
-        strided ones.  Rulebooks depend on indices only, never on features, so
+        layer in `convs` (execution order: spconv.sparse_convs(block)), following the
+        voxel set through the ones that change it -- strided and transposed convs and
+        max-pools to their output sets, an inverse conv back to its couple's input set.
+        Rulebooks depend on indices only, never on features, so
         the whole chain -- including its host reads of output-voxel counts --
         runs before the first feature kernel; the feature pass then finds every
         rulebook in the shared cache.  `strided_outputs` (a list) receives the
-        (indices, spatial_shape) after every strided conv, in order."""
+        (indices, spatial_shape) after every set-changing layer, in order."""
         t = self
         with plan_batch():
             for conv in convs:
                 if getattr(conv, "conv1x1", False):
                     continue
-                rb = t.find_indice_pair(conv.indice_key) if conv.subm else None
-                if rb is None:
-                    rb = t.cached_rulebook(conv.kernel_size, conv.stride, conv.padding,
-                                           conv.dilation, conv.subm)
-                rb.prepare(need_grad, conv.in_channels, conv.out_channels)
+                if getattr(conv, "inverse", False):
+                    # the couple: planned earlier (this call or an earlier one on this chain),
+                    # or already in the tensor's indice_dict.  Without it the forward pass
+                    # raises; nothing further can be planned.
+                    couple = t.__dict__.get("_plan_keys", {}).get(conv.indice_key) or \
+                        t.find_indice_pair(conv.indice_key)
+                    if couple is None or couple.is_subm or couple.nbr_bwd is None:
+                        break
+                    rb = couple.inverted()
+                else:
+                    rb = t.find_indice_pair(conv.indice_key) if conv.subm else None
+                    if rb is None:
+                        rb = t.cached_rulebook(conv.kernel_size, conv.stride, conv.padding,
+                                               conv.dilation, conv.subm,
+                                               transposed=getattr(conv, "transposed", False),
+                                               output_padding=getattr(conv, "output_padding",
+                                                                      (0, 0, 0)))
+                if not getattr(conv, "is_pool", False):     # (a pool reads nbr_bwd only)
+                    rb.prepare(need_grad, conv.in_channels, conv.out_channels)
                 if not conv.subm:
+                    keys = t.__dict__.get("_plan_keys", {})
                     t = t.shadow_copy()
+                    if conv.indice_key is not None and not getattr(conv, "inverse", False):
+                        t._plan_keys = dict(keys, **{conv.indice_key: rb})
                     t.indices = rb.out_indices
                     t._features = t._features.new_empty((rb.out_indices.shape[0], 0))
                     t.spatial_shape = rb.out_spatial_shape

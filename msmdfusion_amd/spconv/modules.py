@@ -155,13 +155,15 @@ class ToDense(SparseModule):
 
 
 def sparse_convs(block):
-    """The SparseConvolution layers of a block, in call order.  The index pass asks
-    for this list for every block of every step; the module tree does not change
+    """The SparseConvolution layers of a block -- and its SparseMaxPool layers, whose
+    rulebooks the index pass builds too (SparseConvTensor.plan) -- in call order.  The index
+    pass asks for this list for every block of every step; the module tree does not change
     between steps, so the walk (nn.Module.modules(): ~40 us per block, 25 blocks)
     is done once per block object."""
     from .conv import SparseConvolution
+    from .pool import SparseMaxPool
     cached = block.__dict__.get("_msmd_sparse_convs")
     if cached is None:
-        cached = [m for m in block.modules() if isinstance(m, SparseConvolution)]
+        cached = [m for m in block.modules() if isinstance(m, (SparseConvolution, SparseMaxPool))]
         block.__dict__["_msmd_sparse_convs"] = cached
     return cached
