@@ -163,6 +163,85 @@ int msmd_scatter_gather_f32(const float* voxel_feats /* [M, C] */, int num_voxel
                             float* out /* [N, C] */, msmd_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * r1  RoI-aware 3-D pooling (max / avg, fwd + bwd) and points-in-boxes
+ * replaces: roiaware_pool3d_ext.forward  mmdet3d/ops/roiaware_pool3d/src/roiaware_pool3d.cpp:49-90
+ *           (CUDA roiaware_pool3d_kernel.cu:17-275: generate_pts_mask_for_box3d,
+ *            collect_inside_pts_for_box3d, roiaware_maxpool3d / _avgpool3d)
+ *           roiaware_pool3d_ext.backward  roiaware_pool3d.cpp:92-124
+ *           (CUDA roiaware_pool3d_kernel.cu:277-366)
+ *           roiaware_pool3d_ext.points_in_boxes_gpu / _batch
+ *           (CUDA mmdet3d/ops/roiaware_pool3d/src/points_in_boxes_cuda.cu:24-203)
+ * Boxes / RoIs are rows of 7 floats (x, y, z of the bottom centre, w, l, h, rz), points rows
+ * of 3.  The predicate, the voxel of a point and the pooling semantics are pinned in
+ * csrc/roiaware.hip.  out_x/y/z must be 1..256 (MSMD_ERR_UNSUPPORTED otherwise).  A cell is
+ * one (RoI, voxel): cell = r * (out_x*out_y*out_z) + (ix*out_y + iy)*out_z + iz.
+ * ------------------------------------------------------------------------ */
+/* Index half, phase 1: tile_start[0 .. T) <- exclusive offsets of the hits of every (RoI,
+ * 2048-point tile), tile_start[T] <- the total number of hits H, the one value the caller
+ * reads; T = msmd_roiaware_num_tiles().  roi_batch / pts_batch (NULL: all 0): a point is
+ * tested only against the RoIs of its own batch id. */
+size_t msmd_roiaware_num_tiles(int num_rois, int num_points);
+size_t msmd_roiaware_count_workspace_bytes(int num_rois, int num_points);
+int msmd_roiaware_count(const float* rois /* [R, 7] */, const int32_t* roi_batch /* [R] */,
+                        int num_rois, const float* pts /* [P, 3] */,
+                        const int32_t* pts_batch /* [P] */, int num_points,
+                        int32_t* tile_start /* [T + 1] */, void* workspace,
+                        size_t workspace_bytes, msmd_stream_t stream);
+/* Phase 2 (the same geometry, tile_start and H of phase 1): the compact point-list index.
+ * hit_pts[vox_start[cell] ..) = the points of the cell in ascending point index, of which the
+ * first min(size, max_pts_per_voxel - 1) are kept; vox_start has R*V + 1 entries.  The
+ * inverse: inv_cell[pt_start[p] .. pt_start[p+1]) = the cells of p's kept hits in ascending
+ * RoI order.  Nothing is read back. */
+size_t msmd_roiaware_index_workspace_bytes(int num_hits);
+int msmd_roiaware_index(const float* rois, const int32_t* roi_batch, int num_rois,
+                        const float* pts, const int32_t* pts_batch, int num_points, int out_x,
+                        int out_y, int out_z, int max_pts_per_voxel, const int32_t* tile_start,
+                        int num_hits, int32_t* hit_pts /* [H] */,
+                        int32_t* vox_start /* [R*V + 1] */, int64_t* inv_cell /* [H] */,
+                        int32_t* pt_start /* [P + 1] */, void* workspace, size_t workspace_bytes,
+                        msmd_stream_t stream);
+/* Feature half: pooled[cell, c] (mode 0 max + argmax[cell, c], 1 avg) over the index.
+ * ref_writes = 0: every element written (no winner / empty -> 0, argmax -1, argmax may be
+ * NULL); 1: only where the reference writes (max: pooled where a point won, argmax always;
+ * avg: pooled where the count is > 0).  hit_pts may be NULL when the index has no hits. */
+int msmd_roiaware_pool_f32(const float* pts_feature /* [P, C] */, int num_points,
+                           int num_channels, const int32_t* hit_pts, const int32_t* vox_start,
+                           int64_t num_cells, int max_pts_per_voxel, int mode, int ref_writes,
+                           float* pooled /* [cells, C] */, int32_t* argmax /* [cells, C] */,
+                           msmd_stream_t stream);
+/* grad_in[p, c] (= when accumulate is 0, += otherwise) the sum of p's contributions in
+ * ascending RoI order, float32, written once per element (no float atomics). */
+int msmd_roiaware_pool_bwd_f32(const float* grad_out /* [cells, C] */, int64_t num_cells,
+                               int num_channels, const int32_t* vox_start, int max_pts_per_voxel,
+                               const int64_t* inv_cell, const int32_t* pt_start, int num_points,
+                               const int32_t* argmax /* [cells, C], max only */, int mode,
+                               int accumulate, float* grad_in /* [P, C] */, msmd_stream_t stream);
+/* The reference's pts_idx_of_voxels [cells, max_pts_per_voxel]: slot 0 = count, slots
+ * 1..count = the points; other slots keep the caller's values. */
+int msmd_roiaware_write_table(const int32_t* hit_pts, const int32_t* vox_start,
+                              int64_t num_cells, int max_pts_per_voxel,
+                              int32_t* pts_idx_of_voxels, msmd_stream_t stream);
+/* The index rebuilt from a caller's padded table (the shim's backward): phase 1 writes
+ * vox_start[0 .. cells] from the counts (clamped to 0 .. max_pts_per_voxel - 1; the total E
+ * at vox_start[cells], read by the caller); phase 2 fills hit_pts[E] and the inverse.  Table
+ * entries outside [0, num_points) are left out of the inverse.  One workspace query for both
+ * phases (phase 1: num_entries = 0). */
+size_t msmd_roiaware_table_workspace_bytes(int64_t num_cells, int num_entries);
+int msmd_roiaware_table_count(const int32_t* pts_idx_of_voxels, int64_t num_cells,
+                              int max_pts_per_voxel, int32_t* vox_start /* [cells + 1] */,
+                              void* workspace, size_t workspace_bytes, msmd_stream_t stream);
+int msmd_roiaware_table_index(const int32_t* pts_idx_of_voxels, int64_t num_cells,
+                              int max_pts_per_voxel, int num_points, int num_entries,
+                              const int32_t* vox_start, int32_t* hit_pts /* [E] */,
+                              int64_t* inv_cell /* [E] */, int32_t* pt_start /* [P + 1] */,
+                              void* workspace, size_t workspace_bytes, msmd_stream_t stream);
+/* points_in_boxes_gpu (all_hits 0): out[b, i] = first box k holding point i, else -1 (every
+ * element written); points_in_boxes_batch (all_hits 1): out[b, i, k] = 0 / 1. */
+int msmd_points_in_boxes_f32(const float* boxes /* [B, T, 7] */, const float* pts /* [B, M, 3] */,
+                             int batch_size, int num_boxes, int num_points, int all_hits,
+                             int32_t* out, msmd_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * a5  Submanifold rulebook (hash-based voxel index)
  * replaces: sparse_conv_ext.get_indice_pairs_3d(..., subM=1)
  *           mmdet3d/ops/spconv/src/all.cc:21-27,

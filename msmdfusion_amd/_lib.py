@@ -53,6 +53,19 @@ SIGNATURES = {
     "msmd_scatter_reduce_bwd_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "msmd_scatter_max_argmax_f32": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "msmd_scatter_gather_f32": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
+    "msmd_roiaware_num_tiles": (_sz, [_i, _i]),
+    "msmd_roiaware_count_workspace_bytes": (_sz, [_i, _i]),
+    "msmd_roiaware_count": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    "msmd_roiaware_index_workspace_bytes": (_sz, [_i]),
+    "msmd_roiaware_index": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp,
+                                 _vp, _vp, _sz, _vp]),
+    "msmd_roiaware_pool_f32": (_i, [_vp, _i, _i, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
+    "msmd_roiaware_pool_bwd_f32": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
+    "msmd_roiaware_write_table": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
+    "msmd_roiaware_table_workspace_bytes": (_sz, [_i64, _i]),
+    "msmd_roiaware_table_count": (_i, [_vp, _i64, _i, _vp, _vp, _sz, _vp]),
+    "msmd_roiaware_table_index": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "msmd_points_in_boxes_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "msmd_rulebook_subm_workspace_bytes": (_sz, [_i]),
     "msmd_rulebook_subm3d": (_i, [_vp, _i, _i, _ip, _ip, _vp, _vp, _sz, _vp]),
     "msmd_rulebook_subm_bitmap_workspace_bytes": (_sz, [_i, _i, _ip]),

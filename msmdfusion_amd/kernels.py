@@ -366,6 +366,238 @@ def scatter_gather(voxel_feats, point2voxel):
     return out
 
 
+# ------------------------------------------------------------------ RoI-aware pooling
+ROIAWARE_MODES = {"max": 0, "avg": 1}
+ROIAWARE_MAX_OUT = 256
+
+
+def roiaware_out_size(out_size):
+    """int or 3-sequence -> (out_x, out_y, out_z), each 1..256 (the reference packs 8 bits per
+    axis and aliases above 256: refused here)."""
+    if isinstance(out_size, int):
+        o = (out_size,) * 3
+    else:
+        o = tuple(out_size)
+        if len(o) != 3 or not all(isinstance(v, int) for v in o):
+            raise ValueError("out_size must be an int or a tuple of 3 ints, got %r" % (out_size,))
+    if not all(1 <= v <= ROIAWARE_MAX_OUT for v in o):
+        raise ValueError("out_size %r: every axis must be 1..%d" % (out_size, ROIAWARE_MAX_OUT))
+    return o
+
+
+def _need_rows(t, width, what, dtype=torch.float32):
+    _need_dtype(t, dtype, what)
+    if t.dim() != 2 or t.shape[1] != width or not t.is_contiguous():
+        raise RuntimeError("%s must be a contiguous [N, %d] %s tensor, got %s"
+                           % (what, width, dtype, tuple(t.shape)))
+
+
+def _need_ids(t, n, what):
+    if t is None:
+        return
+    _need_dtype(t, torch.int32, what)
+    if t.dim() != 1 or t.shape[0] != n or not t.is_contiguous():
+        raise RuntimeError("%s must be a contiguous [%d] int32 tensor" % (what, n))
+
+
+class RoIPointIndex:
+    """The index half of RoI-aware pooling, a function of the RoIs and points alone:
+    hit_pts[H] (the points of every (RoI, voxel) cell in ascending point index, the first
+    min(count, max_pts_per_voxel - 1) of them kept), vox_start[R*V + 1], and the inverse
+    inv_cell[H] / pt_start[P + 1] (each point's kept cells in ascending RoI order).  Every
+    pooling over the same RoIs and points reuses it, whatever its mode and channels."""
+
+    __slots__ = ("hit_pts", "vox_start", "inv_cell", "pt_start", "num_rois", "num_points",
+                 "out_size", "max_pts_per_voxel", "rows")
+
+    def __init__(self, hit_pts, vox_start, inv_cell, pt_start, num_rois, num_points, out_size,
+                 max_pts_per_voxel, rows=None):
+        self.hit_pts, self.vox_start = hit_pts, vox_start
+        self.inv_cell, self.pt_start = inv_cell, pt_start
+        self.num_rois, self.num_points = num_rois, num_points
+        self.out_size, self.max_pts_per_voxel = tuple(out_size), max_pts_per_voxel
+        self.rows = rows          # the RoI rows an extractor selected, in output order
+
+    @property
+    def num_cells(self):
+        ox, oy, oz = self.out_size
+        return self.num_rois * ox * oy * oz
+
+    def counts(self):
+        """Kept points per cell, [R, X, Y, Z] int32."""
+        n = (self.vox_start[1:] - self.vox_start[:-1]).clamp_(max=self.max_pts_per_voxel - 1)
+        return n.view(self.num_rois, *self.out_size)
+
+
+def roiaware_index(rois, pts, out_size, max_pts_per_voxel, roi_batch=None, pts_batch=None):
+    """rois[R, 7], pts[P, 3] float32 (+ int32 batch ids, None: all 0) -> RoIPointIndex.  One
+    launch set for the whole batch and one host read (the hit count)."""
+    _need_cuda(rois, pts, roi_batch, pts_batch)
+    _need_rows(rois, 7, "rois")
+    _need_rows(pts, 3, "pts")
+    ox, oy, oz = roiaware_out_size(out_size)
+    if int(max_pts_per_voxel) < 1:
+        raise ValueError("max_pts_per_voxel must be >= 1")
+    r, n = rois.shape[0], pts.shape[0]
+    _need_ids(roi_batch, r, "roi_batch")
+    _need_ids(pts_batch, n, "pts_batch")
+    dev = rois.device
+    tiles = int(lib.msmd_roiaware_num_tiles(r, n))
+    tile_start = torch.empty((tiles + 1,), dtype=torch.int32, device=dev)
+    nbytes = lib.msmd_roiaware_count_workspace_bytes(r, n)
+    ws = _ws(nbytes, dev)
+    check(lib.msmd_roiaware_count(_p(rois), _p(roi_batch), r, _p(pts), _p(pts_batch), n,
+                                  _p(tile_start), _p(ws), nbytes, _stream()), "msmd_roiaware_count")
+    h = int(tile_start[tiles].item())
+    cells = r * ox * oy * oz
+    hit_pts = torch.empty((h,), dtype=torch.int32, device=dev)
+    inv_cell = torch.empty((h,), dtype=torch.int64, device=dev)
+    vox_start = torch.empty((cells + 1,), dtype=torch.int32, device=dev)
+    pt_start = torch.empty((n + 1,), dtype=torch.int32, device=dev)
+    nbytes = lib.msmd_roiaware_index_workspace_bytes(h)
+    ws = _ws(nbytes, dev)
+    check(lib.msmd_roiaware_index(_p(rois), _p(roi_batch), r, _p(pts), _p(pts_batch), n, ox, oy, oz,
+                                  int(max_pts_per_voxel), _p(tile_start), h, _p(hit_pts),
+                                  _p(vox_start), _p(inv_cell), _p(pt_start), _p(ws), nbytes,
+                                  _stream()), "msmd_roiaware_index")
+    return RoIPointIndex(hit_pts, vox_start, inv_cell, pt_start, r, n, (ox, oy, oz),
+                         int(max_pts_per_voxel))
+
+
+def _roiaware_mode(mode):
+    if mode not in ROIAWARE_MODES:
+        raise ValueError("mode must be 'max' or 'avg', got %r" % (mode,))
+    return ROIAWARE_MODES[mode]
+
+
+def roiaware_pool(pts_feature, index, mode, pooled=None, argmax=None):
+    """pts_feature[P, C] -> (pooled[R, X, Y, Z, C], argmax[R, X, Y, Z, C] int32 | None).
+    With `pooled` (and `argmax` for max) given, writes into them only where the reference
+    kernels write (the shim's in-place contract)."""
+    code = _roiaware_mode(mode)
+    _need_cuda(pts_feature, index.vox_start, pooled, argmax)
+    _need_feats(pts_feature, index.num_points, "pts_feature")
+    c = pts_feature.shape[1]
+    shape = (index.num_rois,) + index.out_size + (c,)
+    ref_writes = pooled is not None
+    if pooled is None:
+        pooled = torch.empty(shape, dtype=torch.float32, device=pts_feature.device)
+        if code == 0:
+            argmax = torch.empty(shape, dtype=torch.int32, device=pts_feature.device)
+    if code == 0 and argmax is None:
+        raise RuntimeError("max pooling needs an argmax tensor")
+    checks = [(pooled, torch.float32, "pooled_features")]
+    if code == 0:
+        checks.append((argmax, torch.int32, "argmax"))
+    for t, dt, what in checks:
+        _need_dtype(t, dt, what)
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise RuntimeError("%s must be a contiguous %s tensor" % (what, shape))
+    check(lib.msmd_roiaware_pool_f32(_p(pts_feature), index.num_points, c, _p(index.hit_pts),
+                                     _p(index.vox_start), index.num_cells,
+                                     index.max_pts_per_voxel, code, int(ref_writes), _p(pooled),
+                                     _p(argmax if code == 0 else None), _stream()),
+          "msmd_roiaware_pool_f32")
+    return pooled, (argmax if code == 0 else None)
+
+
+def roiaware_pool_backward(grad_out, index, mode, argmax=None, grad_in=None):
+    """d pts_feature[P, C] from d pooled[R, X, Y, Z, C]: each point's kept hits summed in
+    ascending RoI order (bitwise reproducible).  With `grad_in` given, adds into it."""
+    code = _roiaware_mode(mode)
+    _need_cuda(grad_out, index.vox_start, argmax, grad_in)
+    _need_dtype(grad_out, torch.float32, "grad_out")
+    g = grad_out.contiguous()
+    if g.dim() != 5 or tuple(g.shape[:4]) != (index.num_rois,) + index.out_size:
+        raise RuntimeError("grad_out must be [%d, %d, %d, %d, C]"
+                           % ((index.num_rois,) + index.out_size))
+    c = g.shape[4]
+    if code == 0:
+        if argmax is None or argmax.dtype != torch.int32 or argmax.shape != g.shape:
+            raise RuntimeError("max backward needs argmax[R, X, Y, Z, C] int32")
+        argmax = argmax.contiguous()
+    accumulate = grad_in is not None
+    if grad_in is None:
+        grad_in = torch.empty((index.num_points, c), dtype=torch.float32, device=g.device)
+    else:
+        _need_feats(grad_in, index.num_points, "grad_in")
+        if grad_in.shape[1] != c:
+            raise RuntimeError("grad_in has %d channels, grad_out %d" % (grad_in.shape[1], c))
+    check(lib.msmd_roiaware_pool_bwd_f32(_p(g), index.num_cells, c, _p(index.vox_start),
+                                         index.max_pts_per_voxel, _p(index.inv_cell),
+                                         _p(index.pt_start), index.num_points,
+                                         _p(argmax if code == 0 else None), code, int(accumulate),
+                                         _p(grad_in), _stream()), "msmd_roiaware_pool_bwd_f32")
+    return grad_in
+
+
+def roiaware_write_table(index, table):
+    """Fill the reference's pts_idx_of_voxels[R, X, Y, Z, max_pts_per_voxel] int32 in place:
+    slot 0 = count, slots 1..count = the points, the rest untouched."""
+    _need_cuda(table, index.vox_start)
+    _need_dtype(table, torch.int32, "pts_idx_of_voxels")
+    shape = (index.num_rois,) + index.out_size + (index.max_pts_per_voxel,)
+    if tuple(table.shape) != shape or not table.is_contiguous():
+        raise RuntimeError("pts_idx_of_voxels must be a contiguous %s int32 tensor" % (shape,))
+    check(lib.msmd_roiaware_write_table(_p(index.hit_pts), _p(index.vox_start), index.num_cells,
+                                        index.max_pts_per_voxel, _p(table), _stream()),
+          "msmd_roiaware_write_table")
+    return table
+
+
+def roiaware_index_from_table(table, num_points):
+    """RoIPointIndex of a padded pts_idx_of_voxels[R, X, Y, Z, M] table (one host read: the
+    number of entries)."""
+    _need_cuda(table)
+    _need_dtype(table, torch.int32, "pts_idx_of_voxels")
+    if table.dim() != 5 or not table.is_contiguous():
+        raise RuntimeError("pts_idx_of_voxels must be a contiguous [N, X, Y, Z, M] int32 tensor")
+    r, ox, oy, oz, m = (int(v) for v in table.shape)
+    roiaware_out_size((ox, oy, oz))
+    if m < 1:
+        raise ValueError("max_pts_per_voxel must be >= 1")
+    dev = table.device
+    cells = r * ox * oy * oz
+    vox_start = torch.empty((cells + 1,), dtype=torch.int32, device=dev)
+    nbytes = lib.msmd_roiaware_table_workspace_bytes(cells, 0)
+    ws = _ws(nbytes, dev)
+    check(lib.msmd_roiaware_table_count(_p(table), cells, m, _p(vox_start), _p(ws), nbytes,
+                                        _stream()), "msmd_roiaware_table_count")
+    e = int(vox_start[cells].item())
+    hit_pts = torch.empty((e,), dtype=torch.int32, device=dev)
+    inv_cell = torch.empty((e,), dtype=torch.int64, device=dev)
+    pt_start = torch.empty((int(num_points) + 1,), dtype=torch.int32, device=dev)
+    nbytes = lib.msmd_roiaware_table_workspace_bytes(cells, e)
+    ws = _ws(nbytes, dev)
+    check(lib.msmd_roiaware_table_index(_p(table), cells, m, int(num_points), e, _p(vox_start),
+                                        _p(hit_pts), _p(inv_cell), _p(pt_start), _p(ws), nbytes,
+                                        _stream()), "msmd_roiaware_table_index")
+    return RoIPointIndex(hit_pts, vox_start, inv_cell, pt_start, r, int(num_points), (ox, oy, oz), m)
+
+
+def points_in_boxes(boxes, pts, all_hits, out=None):
+    """boxes[B, T, 7], pts[B, M, 3] float32 -> [B, M] first box or -1 (all_hits False) or
+    [B, M, T] 0/1 flags (True), int32; written into `out` when given."""
+    _need_cuda(boxes, pts, out)
+    for t, w, what in ((boxes, 7, "boxes"), (pts, 3, "points")):
+        _need_dtype(t, torch.float32, what)
+        if t.dim() != 3 or t.shape[2] != w or not t.is_contiguous():
+            raise RuntimeError("%s must be a contiguous [B, N, %d] float32 tensor, got %s"
+                               % (what, w, tuple(t.shape)))
+    if boxes.shape[0] != pts.shape[0]:
+        raise RuntimeError("points and boxes need the same batch size, got %d and %d"
+                           % (pts.shape[0], boxes.shape[0]))
+    b, m, t = pts.shape[0], pts.shape[1], boxes.shape[1]
+    shape = (b, m, t) if all_hits else (b, m)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int32, device=pts.device)
+    elif out.dtype != torch.int32 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise RuntimeError("box_idxs_of_pts must be a contiguous %s int32 tensor" % (shape,))
+    check(lib.msmd_points_in_boxes_f32(_p(boxes), _p(pts), b, t, m, int(bool(all_hits)), _p(out),
+                                       _stream()), "msmd_points_in_boxes_f32")
+    return out
+
+
 # ------------------------------------------------------------------ rulebooks
 def conv_output_size(in_shape, ksize, stride, padding, dilation=(1, 1, 1)):
     """mmdet3d/ops/spconv/ops.py:20-30."""

@@ -56,6 +56,7 @@ VOXEL_ENCODERS = Registry("voxel_encoder")
 BACKBONES = Registry("backbone")
 NECKS = Registry("neck")
 DETECTORS = Registry("detector")
+ROI_EXTRACTORS = Registry("roi_extractor")
 
 CONV_LAYERS.register_module("Conv1d", module=nn.Conv1d)
 CONV_LAYERS.register_module("Conv2d", module=nn.Conv2d)
@@ -122,3 +123,9 @@ def build_neck(cfg):
     """mmdet3d.models.builder.build_neck for the BEV tail (SECONDFPN)."""
     _register_hot_path()
     return NECKS.build(cfg)
+
+
+def build_roi_extractor(cfg):
+    """mmdet.models.builder.build_roi_extractor (Part-A2's Single3DRoIAwareExtractor)."""
+    from . import roiaware_pool3d  # noqa: F401
+    return ROI_EXTRACTORS.build(cfg)
