@@ -516,12 +516,11 @@ int msmd_spconv_fwd_split_stats_blocks(int n_out, int c_out);
 /* Rows per tile the split kernel uses for a layer of c_out output channels: 256 (the
  * ping-pong form: 8 waves, one workgroup and one weight stream per CU; 161..192 channels as
  * one 12-tile pass) from 161 channels up, 128 below -- the rows_per_tile to compute its
- * tile_prefix with.  Environment: MSMD_FWD_PP_MIN moves the threshold, MSMD_FWD_PP=0 = 128
- * everywhere. */
+ * tile_prefix with. */
 int msmd_spconv_fwd_split_tile_rows(int c_out);
 
 /* Which instantiation of the split kernel msmd_spconv_fwd_split launches for a layer of c_out
- * output channels (under the current environment): params[7] = {NT column tiles per pass,
+ * output channels: params[7] = {NT column tiles per pass,
  * UB units per item, waves per workgroup, weight buffers, ping-pong 0|1, table buffers,
  * column passes = kernel launches per call}.  rocprofv3 names the kernel
  * spconv_fwd_split_kernel<NT, UB, planes, waves, buffers, pingpong, tables>.  For tools
@@ -596,10 +595,9 @@ int msmd_rulebook_permute_cols(const int32_t* nbr, int kernel_volume, int ld, in
  * persistent conv kernels balance best on; `order` may be NULL (natural order).
  * Both only choose a tiling: conv results do not depend on it. */
 /* The whole tiling of a table in one call: order[p] = output row at tile position p
- * (rows sorted by msmd_rulebook_row_masks' key, full tiles re-sequenced by
- * msmd_rulebook_tile_costs, a partial last tile stays last) and, if `tiled` is not
- * NULL, tiled[k][p] = nbr[k][order[p]] (= msmd_rulebook_permute_cols).  In-library
- * radix sorts over the key's significant bits; kernel_volume <= 31, nbr is [K,n_rows]. */
+ * (rows sorted by msmd_rulebook_row_masks' key) and, if `tiled` is not NULL,
+ * tiled[k][p] = nbr[k][order[p]] (= msmd_rulebook_permute_cols).  An in-library radix sort
+ * over the key's significant bits; kernel_volume <= 31, nbr is [K,n_rows]. */
 size_t msmd_rulebook_tiling_workspace_bytes(int n_rows, int rows_per_tile);
 int msmd_rulebook_tiling(const int32_t* nbr, int kernel_volume, int n_rows,
                          int rows_per_tile, int32_t* order /* [n_rows] */,
@@ -623,8 +621,8 @@ int msmd_rulebook_plan(const int32_t* nbr, int kernel_volume, int n_rows,
  * descs: HOST array.  Per table: order is required, tiled / prefix128 / prefix256 /
  * indice_pairs (+ indice_num) / segtab optional (NULL); prefixes need tiled, segtab needs
  * indice_pairs; ld >= n_rows.  Results identical to the single calls.  Tables the launch
- * set cannot take (kernel volumes whose key needs more than 27 bits, empty tables,
- * MSMD_TILE_LPT=1) run through the single calls inside. */
+ * set cannot take (kernel volumes whose key needs more than 27 bits, empty tables) run
+ * through the single calls inside. */
 typedef struct msmd_plan_desc {
   const int32_t* nbr;        /* [K, n_rows] */
   int32_t kvol, n_rows;

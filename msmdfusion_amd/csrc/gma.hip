@@ -23,8 +23,6 @@
 // Python wrapper falls back to the unfused ops when they ask for one.
 #include "common.hpp"
 
-#include <stdlib.h>
-
 namespace msmd {
 namespace {
 
@@ -209,20 +207,15 @@ bool fill_args(GmaArgs& A, const float* conv3, int n_o3, int c3, const float* cr
 // rows per block, forward (whole passes of 32..128) / backward (one partial each).  128 / 128:
 // with 256 the 60-150 k-row tables gave every CU ONE 4-wave workgroup -- a single wave per SIMD
 // waiting out its own LDS latencies -- and the 128-channel backward pass took 75 us; at 128
-// rows it takes 49 (the partials' reduction 6 -> 11 us); MSMD_LIN_FWD_ROWS / _BWD_ROWS.
-inline int lin_env(const char* name, int dflt) {
-  const char* e = getenv(name);
-  const int v = e ? atoi(e) : dflt;
-  return v >= 64 && v <= 1024 && v % 64 == 0 ? v : dflt;
-}
-inline int lin_fwd_rows() { static const int v = lin_env("MSMD_LIN_FWD_ROWS", 128); return v; }
-inline int lin_bwd_rows() { static const int v = lin_env("MSMD_LIN_BWD_ROWS", 128); return v; }
+// rows it takes 49 (the partials' reduction 6 -> 11 us).
+constexpr int kLinRowsPerBlock = 128;
+constexpr int kLinBwdRows = 128;
 constexpr int kLinBwdTile = 32;         // ... staged in LDS this many at a time
 
 __global__ __launch_bounds__(256) void rows_linear_fwd_kernel(
     const float* __restrict__ x, int n, const float* __restrict__ x_tail, int n_tail, int cin,
     const float* __restrict__ w, const float* __restrict__ b, int cout, int relu,
-    float* __restrict__ y, int kLinRowsPerBlock) {
+    float* __restrict__ y) {
   extern __shared__ __attribute__((aligned(16))) float lin_smem[];
   constexpr int RT = 4;                      // rows per thread: a W piece read from LDS serves 4
   float* wt = lin_smem;                      // [cin][cout]: W transposed
@@ -307,7 +300,7 @@ template <int CPT>
 __global__ __launch_bounds__(256) void rows_linear_bwd_partial_kernel(
     const float* __restrict__ x, int n, const float* __restrict__ x_tail, int n_tail, int cin,
     const float* __restrict__ y, const float* __restrict__ dy, int cout, int relu,
-    float* __restrict__ part, int kLinBwdRows) {
+    float* __restrict__ part) {
   extern __shared__ __attribute__((aligned(16))) float lin_smem[];
   const int xs_ld = cin + 4;
   float* gs = lin_smem;                         // [tile][cout]
@@ -523,14 +516,13 @@ MSMD_EXPORT int msmd_rows_linear_fwd_f32(const float* x, int n, const float* x_t
   static LdsGrant granted;
   const int rc = optin_dynamic_lds((const void*)rows_linear_fwd_kernel, smem, granted);
   if (rc != MSMD_OK) return rc;
-  const int kLinRowsPerBlock = lin_fwd_rows();
   MSMD_LAUNCH(rows_linear_fwd_kernel, dim3(ceil_div(total, kLinRowsPerBlock)), dim3(256), smem, st,
-              x, n, x_tail, n_tail, cin, w, b, cout, relu, y, kLinRowsPerBlock);
+              x, n, x_tail, n_tail, cin, w, b, cout, relu, y);
   return launch_status();
 }
 
 MSMD_EXPORT size_t msmd_rows_linear_bwd_workspace_bytes(int n_total, int cin, int cout) {
-  const size_t nblk = ceil_div(n_total > 0 ? n_total : 1, lin_bwd_rows());
+  const size_t nblk = ceil_div(n_total > 0 ? n_total : 1, kLinBwdRows);
   return align_up(sizeof(float) * nblk * ((size_t)cout * cin + cout));
 }
 
@@ -550,7 +542,6 @@ MSMD_EXPORT int msmd_rows_linear_bwd_f32(const float* x, int n, const float* x_t
     return launch_status();
   }
   if (!dy || (relu && !y)) return MSMD_ERR_INVALID_ARG;
-  const int kLinBwdRows = lin_bwd_rows();
   const int nblk = ceil_div(total, kLinBwdRows);
   if (workspace_bytes < sizeof(float) * (size_t)nblk * entries || ((uintptr_t)workspace & 255))
     return MSMD_ERR_WORKSPACE;
@@ -559,7 +550,7 @@ MSMD_EXPORT int msmd_rows_linear_bwd_f32(const float* x, int n, const float* x_t
   const size_t smem = sizeof(float) * ((size_t)kLinBwdTile * cout + (size_t)kLinBwdTile * (cin + 4));
 #define MSMD_LIN_BWD(C_)                                                                       \
   MSMD_LAUNCH(rows_linear_bwd_partial_kernel<C_>, dim3(nblk), dim3(256), smem, st, x, n, x_tail, \
-              n_tail, cin, y, dy, cout, relu, part, kLinBwdRows)
+              n_tail, cin, y, dy, cout, relu, part)
   switch (cpt) {
     case 4: MSMD_LIN_BWD(4); break;
     case 8: MSMD_LIN_BWD(8); break;

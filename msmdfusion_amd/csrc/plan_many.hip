@@ -18,8 +18,6 @@
 #include "scan.hpp"
 #include "tiling_key.hpp"
 
-#include <stdlib.h>
-
 namespace msmd {
 int stream_k_c1();                                   // spconv_split.hip
 size_t wgrad_segment_table_ints(int kvol, int nchunk);   // spconv_wgrad_block.hip
@@ -277,15 +275,9 @@ void carve_many(A& a, ManyWs* w, long rows, long pair_blocks) {
   if (w) *w = ManyWs{keys, keys_out, vals, sorted, sums, cub, cb};
 }
 
-inline bool lpt_mode() {
-  static const int lpt = [] { const char* e = getenv("MSMD_TILE_LPT"); return e ? atoi(e) : 0; }();
-  return lpt != 0;
-}
-
 // tables the launch set takes (the others go through msmd_rulebook_plan one by one)
 inline bool batchable(const msmd_plan_desc& d) {
-  return d.n_rows > 0 && d.kvol >= 1 && d.kvol <= kPlanMaxK && row_key_bits(d.kvol) <= 27 &&
-         !lpt_mode();
+  return d.n_rows > 0 && d.kvol >= 1 && d.kvol <= kPlanMaxK && row_key_bits(d.kvol) <= 27;
 }
 
 inline int check_desc(const msmd_plan_desc& d) {
@@ -303,7 +295,7 @@ size_t single_bytes(const msmd_plan_desc& d) {
   return msmd_rulebook_plan_workspace_bytes(d.kvol, d.n_rows, 128);
 }
 
-// msmd_rulebook_plan + the segment table for one table (not batchable, or LPT mode)
+// msmd_rulebook_plan + the segment table for one table that is not batchable
 int plan_single(const msmd_plan_desc& d, void* ws, size_t ws_bytes, hipStream_t st) {
   hipStream_t stream = st;
   if (d.n_rows == 0) {

@@ -11,7 +11,6 @@
 #include "common.hpp"
 
 #include <math.h>
-#include <stdlib.h>
 
 #include <type_traits>
 #include <utility>
@@ -567,13 +566,6 @@ int fps_block_size(int n) {  // opt_n_threads, furthest_point_sample_cuda.cu:11-
 using namespace msmd;
 
 namespace {
-bool fps_prune_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("MSMD_FPS_PRUNE");   // 0: the plain every-point kernel
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
 void launch_fps_plain(const float* xyz, const int* offsets, int b, int n_max, int n_fixed, int m,
                       float* temp, int32_t* idx, int resume, hipStream_t st) {
   const int ppt = ceil_div(n_max, 1024);
@@ -597,7 +589,7 @@ int launch_fps(const float* xyz, const int* offsets, int b, int n_max, int n_fix
   // registers).  It may hand an element over (see kFpsProbe1): the plain kernel runs
   // right behind it in resume mode and returns at once for finished elements.
   const int ppl = ceil_div(n_max, kFpsPrunedThreads);
-  if (fps_prune_enabled() && n_max >= 6144 && ppl <= 48 && m > 2 * kFpsProbe1) {
+  if (n_max >= 6144 && ppl <= 48 && m > 2 * kFpsProbe1) {
 #define FPSP(P)                                                                              \
   MSMD_LAUNCH(fps_pruned_kernel<P>, dim3(b), dim3(kFpsPrunedThreads), 0, st, xyz, offsets, \
               n_fixed, m, idx)

@@ -28,9 +28,6 @@
 #include "common.hpp"
 #include "tiling_key.hpp"
 
-#include <stdlib.h>
-#include <string.h>
-
 namespace msmd {
 namespace {
 
@@ -77,7 +74,7 @@ __global__ __launch_bounds__(256) void spconv_fwd_kernel(
     const float* __restrict__ in, int cin, const float* __restrict__ wp,
     const int32_t* __restrict__ nbr, int ld, int n_out, int kvol, int flip,
     const int32_t* __restrict__ order, int* __restrict__ tile_counter, float* __restrict__ out,
-    int cout, int dbg) {
+    int cout) {
   __shared__ f32x4 wl[kTC * NT * 64];
   __shared__ int s_tile;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -136,10 +133,8 @@ __global__ __launch_bounds__(256) void spconv_fwd_kernel(
         const int tc = (T - t0) < kTC ? (T - t0) : kTC;
         // ---- stage W[kw][t0 .. t0+tc) : tc*NT*64 float4, straight copy ----
         if (t0 > 0) __syncthreads();
-        if (!(dbg & 2)) {
-          const f32x4* g = (const f32x4*)wp + ((size_t)kw * T + t0) * NT * 64;
-          for (int e = threadIdx.x; e < tc * NT * 64; e += 256) wl[e] = g[e];
-        }
+        const f32x4* g = (const f32x4*)wp + ((size_t)kw * T + t0) * NT * 64;
+        for (int e = threadIdx.x; e < tc * NT * 64; e += 256) wl[e] = g[e];
         // ---- gather this wave's input rows (overlaps the fill) ----
         f32x4 b[R][kTC];
         if (wave_any) {
@@ -149,7 +144,7 @@ __global__ __launch_bounds__(256) void spconv_fwd_kernel(
             for (int t = 0; t < kTC; ++t) {
               f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
               const int c0 = 16 * (t0 + t) + 4 * q;
-              if (t < tc && src[r] >= 0 && !(dbg & 1)) {
+              if (t < tc && src[r] >= 0) {
                 const float* p = in + (size_t)src[r] * cin + c0;
                 if (VEC) {
                   if (c0 < cin) v = *(const f32x4*)p;
@@ -204,15 +199,9 @@ __global__ __launch_bounds__(256) void spconv_fwd_kernel(
   }
 }
 
-// Tuning constants chosen from on-device sweeps (round-1 sweep script, since pruned: git history; the environment
-// overrides of rounds 1-2 -- MSMD_FWD_SLOTS / _R / _PIPE / _KC, MSMD_PIPE_MIN_NT,
-// MSMD_NARROW_ORDER, MSMD_WGRAD_MULTISLAB -- are gone: measured, decided).
-inline int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-inline int fwd_slots_per_cu() { return 3; }
-inline int fwd_rows_variant() { return 0; }   // 0 = per-NT default
+// Persistent workgroups per CU of the fp32 forward kernels: chosen from on-device sweeps
+// (DESIGN.md 3.2-3.3).
+constexpr int kFwdSlotsPerCu = 3;
 
 // ---------------------------------------------------- pipelined forward ----
 // Same math and tiling as spconv_fwd_kernel, restructured so that no memory
@@ -410,7 +399,7 @@ int launch_fwd_pipe(const float* in, int cin, const float* wp, const int32_t* nb
   const int n_tiles = ceil_div(n_out, kRows);
   int nblk = n_tiles;
   if (tile_counter) {
-    const int slots = 256 * fwd_slots_per_cu();
+    const int slots = 256 * kFwdSlotsPerCu;
     if (nblk > slots) nblk = slots;
   }
   auto kern = spconv_fwd_pipe_kernel<NT, R, KC>;
@@ -451,17 +440,16 @@ int launch_fwd(const float* in, int cin, const float* wp, const int32_t* nbr, in
   const int n_tiles = ceil_div(n_out, rows_per_block);
   int nblk = n_tiles;
   if (tile_counter) {
-    const int slots = 256 * fwd_slots_per_cu();
+    const int slots = 256 * kFwdSlotsPerCu;
     if (nblk > slots) nblk = slots;
   }
   dim3 grid(nblk);
-  static const int dbg = env_int("MSMD_DBG", 0);  // ablation bits, experiments only
   if ((cin & 3) == 0)
     MSMD_LAUNCH((spconv_fwd_kernel<NT, R, true>), grid, dim3(256), 0, st, in, cin, wp, nbr, ld,
-                n_out, kvol, flip, order, tile_counter, out, cout, dbg);
+                n_out, kvol, flip, order, tile_counter, out, cout);
   else
     MSMD_LAUNCH((spconv_fwd_kernel<NT, R, false>), grid, dim3(256), 0, st, in, cin, wp, nbr, ld,
-                n_out, kvol, flip, order, tile_counter, out, cout, dbg);
+                n_out, kvol, flip, order, tile_counter, out, cout);
   return launch_status();
 }
 
@@ -877,10 +865,10 @@ MSMD_EXPORT int msmd_spconv_fwd_f32(const float* in_feat, int n_in, int c_in,
     case 1: FWD(1, 2);
     case 2: FWD(2, 2);
     case 3: FWD(3, 2);
-    case 4: if (fwd_rows_variant() == 2) FWD(4, 2); else FWD(4, 1);
-    case 5: if (fwd_rows_variant() == 2) FWD(5, 2); else FWD(5, 1);
-    case 6: if (fwd_rows_variant() == 2) FWD(6, 2); else FWD(6, 1);
-    case 8: if (fwd_rows_variant() == 2) FWD(8, 2); else FWD(8, 1);
+    case 4: FWD(4, 1);
+    case 5: FWD(5, 1);
+    case 6: FWD(6, 1);
+    case 8: FWD(8, 1);
     case 12: FWD(12, 1);
     default: break;
   }
@@ -1031,9 +1019,8 @@ MSMD_EXPORT int msmd_spconv_wgrad_split_segments(const float* in_feat, int c_in,
   }
   if (!in_feat || !d_out || !indice_pairs) return MSMD_ERR_INVALID_ARG;
   // the whole c_in x c_out block per workgroup (spconv_wgrad_block.hip) wherever both
-  // widths are multiples of 16; MSMD_WGRAD=var keeps the 64 x 64 slab kernel (A/B runs)
-  static const bool use_block = [] { const char* e = getenv("MSMD_WGRAD"); return !(e && !strcmp(e, "var")); }();
-  if (use_block && wgrad_block_supported(c_in, c_out, kernel_volume, ld) &&
+  // widths are multiples of 16; the 64 x 64 slab kernel otherwise
+  if (wgrad_block_supported(c_in, c_out, kernel_volume, ld) &&
       (double)ld * 4.0 * (c_in > c_out ? c_in : c_out) < 4.0e9) {
     if (workspace_bytes < wgrad_block_workspace_bytes(kernel_volume, c_in, c_out, n_chunks) ||
         ((uintptr_t)workspace & 255))

@@ -26,7 +26,6 @@
 // Forward / dgrad: output-stationary pipelined implicit GEMM (see the kernel).
 #include "common.hpp"
 
-#include <stdlib.h>
 #include <type_traits>
 
 namespace msmd {
@@ -44,11 +43,6 @@ typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void glb_void;
 
 constexpr int kMaxK = 32;
-
-int env_int2(const char* name, int dflt) {
-  const char* s = getenv(name);
-  return s ? atoi(s) : dflt;
-}
 
 // Split 8 fp32 values into NP bf16 planes (round-to-nearest-even at every level).
 template <int NP>
@@ -383,7 +377,7 @@ __global__ __launch_bounds__(WV * 64, WV == 4 ? 2 : 1) void spconv_fwd_split_ker
     const int32_t* __restrict__ order, int* __restrict__ tile_counter, float* __restrict__ out,
     int ldo, int cout, int nt_total, int mt0, f32x4* __restrict__ scratch,
     int* __restrict__ flags, const int32_t* __restrict__ tile_start, int sk_c0, int sk_c1v,
-    int dbg, float* __restrict__ bn_part, int n_ranges) {
+    float* __restrict__ bn_part, int n_ranges) {
   // Scheduling.  Without `tile_start`: persistent workgroups draw whole 128-row tiles from
   // a global counter (tiles arrive heaviest first: LPT list scheduling), every tile is one
   // unit and the result does not depend on the tiling order at all.  A tile whose rows are
@@ -606,11 +600,10 @@ __global__ __launch_bounds__(WV * 64, WV == 4 ? 2 : 1) void spconv_fwd_split_ker
       for (int r = 0; r < R; ++r) {
         const int src = s_next[r];
         valid = src > valid ? src : valid;
-        // (dbg & 8, experiments only: fold the gathers onto 4096 rows -- all L2 hits)
         // (24-bit multiply, full rate: rows < 2^24 and row bytes < 2^24 -- the entry point's
         // range check; the plain product compiled to a quarter-rate 64-bit multiply-add)
-        const unsigned rowb = __umul24((unsigned)((dbg & 8) ? (src & 4095) : src), row_bytes) + col;
-        const unsigned off = (src < 0 || chan0 >= cin || (dbg & 2)) ? kOobOffset : rowb;
+        const unsigned rowb = __umul24((unsigned)src, row_bytes) + col;
+        const unsigned off = (src < 0 || chan0 >= cin) ? kOobOffset : rowb;
         gather_row8(raw[r], off, rs);
       }
       MSMD_ADV(mg, kbg);
@@ -637,25 +630,6 @@ __global__ __launch_bounds__(WV * 64, WV == 4 ? 2 : 1) void spconv_fwd_split_ker
         MSMD_ADV(mw, kbw);
       }
     };
-    // pieces [p0, p1) of the weight image of item `it` (UB == 1; the cursor moves with the
-    // last piece): the ping-pong form may issue some of them from the multiply segment
-    auto issue_w_part = [&](int it, int p0, int p1) {
-      u32x4* wb = wl + (NB == 2 ? (it & 1) : it % NB) * kWU;
-      const int k = mw ? __builtin_ctz(mw) : 0;
-      const int kw = flip ? kvol - 1 - k : k;
-      const u32x4* g = wp + ((size_t)kw * kbt + kbw) * (NP * nt_total * 64);
-#pragma unroll
-      for (int pp = p0; pp < p1; ++pp) {
-        int piece = wave + WV * pp;
-        if ((NP * NT) % WV != 0 && piece >= NP * NT) piece = 0;
-        const int pl = piece / NT;
-        int tile = mt0 + piece - pl * NT;
-        tile = tile < nt_total ? tile : nt_total - 1;
-        __builtin_amdgcn_global_load_lds((glb_void*)(g + (pl * nt_total + tile) * 64 + lane),
-                                         (lds_void*)(wb + piece * 64), 16, 0, 0);
-      }
-      if (p1 == kPw) MSMD_ADV(mw, kbw);
-    };
     auto split_all = [&](const u32x4 (&raw)[R][2], u32x4 (&cv)[R][NP]) {
 #pragma unroll
       for (int r = 0; r < R; ++r)
@@ -669,7 +643,9 @@ __global__ __launch_bounds__(WV * 64, WV == 4 ? 2 : 1) void spconv_fwd_split_ker
     // (called once per fragment step, between two MFMA groups)
     auto compute = [&](int it, int u, const u32x4 (&b)[R][NP], int valid,
                        const u32x4 (&raw_n)[R][2], u32x4 (&b_n)[R][NP], auto&& during) {
-      if (!__any(valid >= 0) || (dbg & 4)) {
+      // (through readfirstlane: with the bare __any the compiler allocates 17-53 more VGPRs
+      // to the 4-wave instantiations, and the 8-tile ones at 2-3 planes spill)
+      if (__builtin_amdgcn_readfirstlane((int)__any(valid >= 0)) == 0) {
 #pragma unroll
         for (int st = 0; st < NS; ++st) during(st);
         split_all(raw_n, b_n);
@@ -741,7 +717,7 @@ __global__ __launch_bounds__(WV * 64, WV == 4 ? 2 : 1) void spconv_fwd_split_ker
       const bool grp_b = wave >= WV / 2;
       // the unit's MFMAs alone (its rows' planes `b` were made in the load segment)
       auto multiply = [&](int it, const u32x4 (&b)[R][NP], int valid) {
-        if (!__any(valid >= 0) || (dbg & 4)) return;
+        if (!__any(valid >= 0)) return;
         const u32x4* wb = wl + (it % NB) * kWU + lane;
         // fragments double-buffered per 16-channel TILE (12 registers a buffer; per PAIR of
         // tiles, as the 4-wave kernel does, costs 24 more and spills the 12-tile instantiation):
@@ -773,14 +749,6 @@ __global__ __launch_bounds__(WV * 64, WV == 4 ? 2 : 1) void spconv_fwd_split_ker
         }
         __builtin_amdgcn_sched_barrier(0);
       };
-      // kWM of an item's kPw weight DMA pieces are issued at the head of the MULTIPLY segment
-      // instead of in the load segment (experiment: -DMSMD_PP_WM=n): the load segment is the
-      // longer one for 6 and 8 column tiles.  The pieces then are the newest operations when
-      // the segment ends: its wait drains the queue.
-#ifndef MSMD_PP_WM
-#define MSMD_PP_WM 0
-#endif
-      constexpr int kWM = (MSMD_PP_WM) < kPw ? (MSMD_PP_WM) : kPw - 1;
       auto pin_planes = [&](u32x4 (&c)[R][NP]) {
 #pragma unroll
         for (int r = 0; r < R; ++r)
@@ -812,12 +780,12 @@ __global__ __launch_bounds__(WV * 64, WV == 4 ? 2 : 1) void spconv_fwd_split_ker
       staged = true;                                                                    \
     }                                                                                   \
     KP_MARK(6);                                                                         \
-    issue_w_part((G) + 1, 0, kPw - kWM);                                                \
+    issue_w((G) + 1);                                                                   \
     KP_MARK(2);                                                                         \
     issue_g(RAW_N, V_N);                                                                \
     load_src();                                                                         \
     KP_MARK(3);                                                                         \
-    wait_rows<kGr + kPw - kWM>(RAW_C);                                                  \
+    wait_rows<kGr + kPw>(RAW_C);                                                        \
     KP_MARK(4);                                                                         \
     split_all(RAW_C, cv);                                                               \
     /* (the conversion belongs to THIS segment: left alone the optimiser sinks it below \
@@ -829,12 +797,9 @@ __global__ __launch_bounds__(WV * 64, WV == 4 ? 2 : 1) void spconv_fwd_split_ker
     __builtin_amdgcn_s_barrier();                                                       \
     __builtin_amdgcn_sched_barrier(0);                                                  \
     KP_MARK(1);                                                                         \
-    if (kWM > 0) issue_w_part((G) + 1, kPw - kWM, kPw);                                 \
-    if (dbg & 32) __builtin_amdgcn_s_setprio(1);                                        \
     multiply((G), cv, V_C);                                                             \
-    if (dbg & 32) __builtin_amdgcn_s_setprio(0);                                        \
     KP_MARK(5);                                                                         \
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kWM > 0 ? 0 : kGr) : "memory");            \
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kGr) : "memory");                          \
     KP_MARK(0);                                                                         \
     __builtin_amdgcn_s_barrier();                                                       \
     KP_MARK(9);                                                                         \
@@ -897,8 +862,6 @@ __global__ __launch_bounds__(WV * 64, WV == 4 ? 2 : 1) void spconv_fwd_split_ker
     KP_MARK(6);                                                                        \
     if (NB == 3 && (IT) >= 4)   /* weights two items ahead: those of IT + 1 stay in flight */ \
       asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(kWp + UB * kGr) : "memory");   \
-    else if (NB == 2 && (dbg & 16) && (IT) >= 1)  /* experiment: the item's own gathers stay in flight */ \
-      asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(UB * kGr) : "memory");         \
     else                                                                               \
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                      \
     KP_MARK(0);                                                                        \
@@ -1094,17 +1057,6 @@ __global__ __launch_bounds__(WV * 64, WV == 4 ? 2 : 1) void spconv_fwd_split_ker
 }
 
 int split_slots_per_cu() { return 2; }
-// CUs the persistent conv kernels leave to the other queues of a step (the index pass of the
-// next batch, the neighbour-search chains): a kernel of theirs that finds every CU holding two
-// conv workgroups (156 of 160 KB of LDS, 476 of 512 registers per SIMD) waits for a conv
-// workgroup to EXIT before it can start.  MSMD_RESERVE_CUS.
-int reserved_cus() {
-  static const int n = [] {
-    const int v = env_int2("MSMD_RESERVE_CUS", 0);
-    return v < 0 ? 0 : v > 128 ? 128 : v;
-  }();
-  return n;
-}
 
 template <int NT, int UB, int NP, int WV, int NB = 2, bool PP = false, int TB = 2>
 int launch_fwd_split(const float* in, int n_in, int cin, const void* wp, const int32_t* nbr,
@@ -1123,7 +1075,7 @@ int launch_fwd_split(const float* in, int n_in, int cin, const void* wp, const i
                       sizeof(int) * (TB * (size_t)(kvol + 1) * kRows + 72);
   const int n_tiles = ceil_div(n_out, kRows);
   int nblk = n_tiles;
-  const int slots = (256 - reserved_cus()) * (WV == 4 ? split_slots_per_cu() : 1);
+  const int slots = 256 * (WV == 4 ? split_slots_per_cu() : 1);
   if (nblk > slots) nblk = slots;
   // stream-K: sk_grid ranges for (at most) one workgroup per slot
   if (tile_start) nblk = sk_grid < slots ? sk_grid : slots;
@@ -1133,8 +1085,7 @@ int launch_fwd_split(const float* in, int n_in, int cin, const void* wp, const i
   if (lds_rc != MSMD_OK) return lds_rc;
   MSMD_LAUNCH(kern, dim3(nblk), dim3(WV * 64), smem, st, in, n_in, cin, (const u32x4*)wp, nbr, ld,
               n_out, kvol, flip, order, tile_counter, out, ldo, cout, nt_total, mt0,
-              (f32x4*)scratch, flags, tile_start, sk_c0, sk_c1(), env_int2("MSMD_DBG", 0), bn_part,
-              sk_grid);
+              (f32x4*)scratch, flags, tile_start, sk_c0, sk_c1(), bn_part, sk_grid);
   return launch_status();
 }
 
@@ -1146,43 +1097,24 @@ int launch_fwd_split(const float* in, int n_in, int cin, const void* wp, const i
 // is within +-5 % of it there (96 -> 128 +3.5 %, 128 -> 128 0, 80 -> 80 -7 %), and inside the
 // LC step -- other streams' kernels wanting CUs that an 8-wave, 130 KiB workgroup holds whole
 // -- its 8-tile instantiation ran 10 % slower (101-104 against 113-114 TF, same call).
-// MSMD_FWD_PP_MIN moves the threshold (97: every layer above 96 channels), MSMD_FWD_PP=0
-// keeps 4 waves everywhere (the round-1..4 kernel), for A/B runs.
 // (History: plain 8-wave / 256-row instantiations -- one barrier per item -- measured within
 // +-5 % on the 128-/192-channel layers and 25 % slower on the 80-channel ones in rounds 2 and
 // 4: the two waves of a SIMD met at every barrier and serialised their MFMA phases.)
-int fwd_pp() {
-  static const int v = env_int2("MSMD_FWD_PP", 1);
-  return v;
-}
-int fwd_waves(int cout) {
-  static const int min_cout = env_int2("MSMD_FWD_PP_MIN", 161);
-  return (fwd_pp() && cout >= min_cout) ? 8 : 4;
-}
+int fwd_waves(int cout) { return cout >= 161 ? 8 : 4; }
 // Column passes: at most 8 tiles of 16 channels each -- except 161..192 channels in the
 // ping-pong form, ONE pass of 12 tiles: a row piece is gathered and split into planes once
 // for all of c_out (two 6-tile passes did that work twice: the load segment of an item --
 // weight DMA, gathers, conversion, ~2400 cycles -- is longer than its 72 MFMAs' 1150).
 int fwd_passes(int cout) {
   const int nt_total = (cout + 15) / 16;
-  static const int one12 = env_int2("MSMD_FWD_NT12", 1);
-  if (fwd_waves(cout) == 8 && one12 && (nt_total == 11 || nt_total == 12)) return 1;
+  if (fwd_waves(cout) == 8 && (nt_total == 11 || nt_total == 12)) return 1;
   return (nt_total + 7) / 8;
 }
 // stream-K: workgroups (= segments = exchange slots) of a launch over `row_tiles` tiles,
 // and the exchange buffer: one pass's accumulators of one tile per workgroup
-// (ranges per workgroup slot: MSMD_SK_MULT)
-int sk_ranges_per_slot() {
-  static const int m = [] {
-    const int v = env_int2("MSMD_SK_MULT", 1);
-    return v < 1 ? 1 : v > 8 ? 8 : v;
-  }();
-  return m;
-}
 int sk_grid_size(int row_tiles, int kvol, int waves) {
   const long ranks_max = (long)row_tiles * kvol;
-  const long ranges = (256L - reserved_cus()) * (waves == 4 ? split_slots_per_cu() : 1) *
-                      sk_ranges_per_slot();
+  const long ranges = 256L * (waves == 4 ? split_slots_per_cu() : 1);
   return (int)(ranks_max < ranges ? ranks_max : ranges);
 }
 size_t fwd_sk_ws_bytes(int n_out, int kvol, int cout) {
@@ -1190,15 +1122,11 @@ size_t fwd_sk_ws_bytes(int n_out, int kvol, int cout) {
   const int n_pass = fwd_passes(cout);
   int per = (nt_total + n_pass - 1) / n_pass;
   per = per > 8 ? 12 : per > 6 ? 8 : per > 4 ? 6 : per > 2 ? 4 : 2;      // the instantiation's NT
-  if (fwd_waves(cout) == 8 && per < 6) per = 6;           // (ping-pong: NT = 6 or 8)
-  size_t need = 0;
-  for (int waves = fwd_waves(cout); waves <= fwd_waves(cout); waves += 4) {
-    const int rows = waves * 32;
-    const size_t b = (size_t)sk_grid_size(ceil_div(n_out > 0 ? n_out : 0, rows), kvol, waves) *
-                     rows * 16 * per * sizeof(float);
-    need = b > need ? b : need;
-  }
-  return need;
+  const int waves = fwd_waves(cout);
+  if (waves == 8 && per < 6) per = 6;           // (ping-pong: NT = 6 or 8)
+  const int rows = waves * 32;
+  return (size_t)sk_grid_size(ceil_div(n_out > 0 ? n_out : 0, rows), kvol, waves) * rows * 16 *
+         per * sizeof(float);
 }
 
 // c_out is covered in passes of at most 128 channels (8 tiles of 16; a pass's
@@ -1216,11 +1144,10 @@ int dispatch_fwd_split(const float* in, int n_in, int cin, const void* wp, const
   const int row_tiles = ceil_div(n_out, waves * 32);
   // Stream-K (see the kernel) whenever the caller passed the tile prefix (computed for this
   // layer's tile size: msmd_spconv_fwd_split_tile_rows) and the exchange buffers cover one
-  // slot / one flag per workgroup; MSMD_STREAMK=0 falls back to the dynamic tile scheduler.
-  static const int sk_on = env_int2("MSMD_STREAMK", 1);
+  // slot / one flag per workgroup; otherwise the dynamic tile scheduler.
   const int sk_grid = sk_grid_size(row_tiles, kvol, waves);
   const int32_t* tile_start = nullptr;
-  if (sk_on && tile_prefix && ws && ws_bytes >= fwd_sk_ws_bytes(n_out, kvol, cout) &&
+  if (tile_prefix && ws && ws_bytes >= fwd_sk_ws_bytes(n_out, kvol, cout) &&
       sync_ints >= 1 + sk_grid) {
     tile_start = tile_prefix;
   }
@@ -1342,7 +1269,7 @@ template <int NP, int WA, int WB>
 __device__ __forceinline__ void wgrad_var_body(
     const float* __restrict__ in, int cin, const float* __restrict__ dout, int cout,
     const unsigned* s_in, const unsigned* s_out, f32x4* red, int a0, int b0, int cnt,
-    float* __restrict__ dst /* [cin][cout] partial of this (k, chunk) */, int dbg) {
+    float* __restrict__ dst /* [cin][cout] partial of this (k, chunk) */) {
   using P = Products<NP>;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = lane & 15, g = lane >> 4;
@@ -1412,17 +1339,6 @@ __device__ __forceinline__ void wgrad_var_body(
     split_side(ra, oa, std::integral_constant<int, WA>{});
     split_side(rb, ob, std::integral_constant<int, WB>{});
     if (step + 4 < n_steps) fetch(step + 4);   // in flight under the MFMAs below
-    if (dbg & 4) {
-#pragma unroll
-      for (int a = 0; a < WA; ++a)
-#pragma unroll
-        for (int pl = 0; pl < NP; ++pl) asm volatile("" ::"v"(oa[a][pl]));
-#pragma unroll
-      for (int b = 0; b < WB; ++b)
-#pragma unroll
-        for (int pl = 0; pl < NP; ++pl) asm volatile("" ::"v"(ob[b][pl]));
-      continue;
-    }
     __builtin_amdgcn_s_setprio(2);
 #pragma unroll
     for (int t = 0; t < P::n; ++t)
@@ -1491,7 +1407,7 @@ template <int NP>
 __global__ __launch_bounds__(256, 2) void spconv_wgrad_split_var_kernel(
     const float* __restrict__ in, int cin, const float* __restrict__ dout, int cout,
     const int32_t* __restrict__ pairs, const int32_t* __restrict__ num, int ld, int nchunks,
-    int kvol, float* __restrict__ partial /* [K][nchunks][cin][cout] */, int dbg) {
+    int kvol, float* __restrict__ partial /* [K][nchunks][cin][cout] */) {
   constexpr int CHUNK = kWgradSplitChunk;
   __shared__ __attribute__((aligned(16))) char lds_raw[2 * 16 * 64 * sizeof(f32x4)];
   unsigned* s_in = (unsigned*)lds_raw;       // BYTE OFFSETS of the rows (or the OOB offset)
@@ -1510,9 +1426,7 @@ __global__ __launch_bounds__(256, 2) void spconv_wgrad_split_var_kernel(
     const int32_t* pout = pairs + ((size_t)k * 2 + 1) * ld + p_begin;
     const unsigned rowa = (unsigned)cin * 4u, rowb = (unsigned)cout * 4u;
     for (int e = threadIdx.x; e < CHUNK; e += 256) {   // past the end: "no pair"
-      int ia = e < cnt ? pin[e] : -1, ib = e < cnt ? pout[e] : -1;
-      if (dbg & 1) { ia = ia < 0 ? ia : (ia & 4095); ib = ib < 0 ? ib : (ib & 4095); }
-      if (dbg & 2) { ia = -1; ib = -1; }
+      const int ia = e < cnt ? pin[e] : -1, ib = e < cnt ? pout[e] : -1;
       s_in[e] = ia >= 0 ? (unsigned)ia * rowa : kOobOffset;
       s_out[e] = ib >= 0 ? (unsigned)ib * rowb : kOobOffset;
     }
@@ -1523,7 +1437,7 @@ __global__ __launch_bounds__(256, 2) void spconv_wgrad_split_var_kernel(
 #define MSMD_VAR_CASE(A, B)                                                                  \
   case A * 8 + B:                                                                            \
     wgrad_var_body<NP, A, B>(in, cin, dout, cout, s_in, s_out, (f32x4*)lds_raw, 64 * sa,     \
-                             64 * sb, cnt, dst, dbg);                                        \
+                             64 * sb, cnt, dst);                                             \
     break
   switch (wa * 8 + wb) {
     MSMD_VAR_CASE(4, 4);
@@ -1741,17 +1655,16 @@ int wgrad_split_partials(const float* in_feat, int c_in, const float* d_out, int
   // 32-bit row offsets (buffer loads): both operands must stay below 4 GiB
   if (!((double)ld * 4.0 * (c_in > c_out ? c_in : c_out) < (double)kOobOffset))
     return MSMD_ERR_RANGE;
-  static const int wdbg = env_int2("MSMD_WGRAD_DBG", 0);
   const dim3 gv(wgrad_grid(nchunks, kvol, wgrad_var_slabs(c_in) * wgrad_var_slabs(c_out)));
   if (np == 3)
     MSMD_LAUNCH(spconv_wgrad_split_var_kernel<3>, gv, dim3(256), 0, st, in_feat, c_in, d_out,
-                c_out, pairs, num, ld, nchunks, kvol, ws, wdbg);
+                c_out, pairs, num, ld, nchunks, kvol, ws);
   else if (np == 2)
     MSMD_LAUNCH(spconv_wgrad_split_var_kernel<2>, gv, dim3(256), 0, st, in_feat, c_in, d_out,
-                c_out, pairs, num, ld, nchunks, kvol, ws, wdbg);
+                c_out, pairs, num, ld, nchunks, kvol, ws);
   else
     MSMD_LAUNCH(spconv_wgrad_split_var_kernel<1>, gv, dim3(256), 0, st, in_feat, c_in, d_out,
-                c_out, pairs, num, ld, nchunks, kvol, ws, wdbg);
+                c_out, pairs, num, ld, nchunks, kvol, ws);
   return launch_status();
 }
 }  // namespace msmd

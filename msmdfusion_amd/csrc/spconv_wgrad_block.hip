@@ -50,8 +50,6 @@
 //     its 27 offsets, the input rows once for the offsets that share them.
 #include "common.hpp"
 
-#include <stdlib.h>
-
 #include <type_traits>
 
 namespace msmd {
@@ -212,7 +210,6 @@ struct BlockArgs {
   int cin, cout, ld, kvol, nchunk;
   int TA, TB, nba, nbb;   // tiles per block and blocks per side
   int min_steps;
-  int dbg;                // experiments: 1 rows folded onto 4096 (cache hits), 2 no row loads
 };
 
 // s_waitcnt lgkmcnt(0) as an INSTRUCTION the compiler's wait-count pass sees (vmcnt 63,
@@ -294,9 +291,6 @@ __device__ __forceinline__ void produce(const BlockArgs& A, const SegTab& tab, C
   const unsigned lane_col = (unsigned)(16 * a0 + N * i) * 4u;   // inside the block
   const int slot_u = (A.TA + A.TB) * NP * 64;                   // u32x4 units per ring slot
   u32x4* dst0 = ring + ((side ? A.TA : 0) + a0) * NP * 64 + lane;
-#ifdef MSMD_WGRAD_BLOCK_DBG
-  const bool fold = A.dbg & 1, norows = A.dbg & 2;
-#endif
 
   u32x4 idx[2];             // pair indices of the next own step but one
   int idx_rem;              // pairs of that step from this lane's first one on (<= 0: none)
@@ -335,15 +329,9 @@ __device__ __forceinline__ void produce(const BlockArgs& A, const SegTab& tab, C
   auto make_offsets = [&]() {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      unsigned r = idx[e >> 2][e & 3];
-#ifdef MSMD_WGRAD_BLOCK_DBG
-      r = fold ? (r & 4095u) : r;
-#endif
+      const unsigned r = idx[e >> 2][e & 3];
       const unsigned o = __umul24(r, row_bytes) + idx_col;   // rows < 2^24 (host check)
       off[e] = e < idx_rem ? o : kOob;
-#ifdef MSMD_WGRAD_BLOCK_DBG
-      off[e] = norows ? kOob : off[e];
-#endif
     }
   };
   auto load_rows = [&](auto slot) {
@@ -358,24 +346,12 @@ __device__ __forceinline__ void produce(const BlockArgs& A, const SegTab& tab, C
   // part 1 of the own step in raw slot S: loads for later own steps, first half converted
   auto part1 = [&](auto slot) {
     constexpr int S = decltype(slot)::value;
-#ifdef MSMD_WGRAD_BLOCK_DBG
-    if (A.dbg & 64) return;     // barriers only
-    if (A.dbg & 128) { make_offsets(); load_idx(); return; }   // no row loads issued at all
-#endif
     make_offsets();                      // next own step (indices loaded one own step ago)
     __builtin_amdgcn_sched_barrier(0);
     load_idx();                          // the own step after next
     __builtin_amdgcn_sched_barrier(0);
     load_rows(ic<S ^ 1>{});              // next own step
     if (wb_on) WB_MARK(0);
-#ifdef MSMD_WGRAD_BLOCK_DBG
-    if (A.dbg & 4) {   // no conversion: raw bits as operands (wrong results by design)
-#pragma unroll
-      for (int a = 0; a < N; ++a)
-#pragma unroll
-        for (int pl = 0; pl < NP; ++pl) op[a][pl] = (u32x4){raw[S][0][a], raw[S][1][a], raw[S][2][a], raw[S][3][a]};
-    } else
-#endif
     split_rows<NP, N, 0, 2>(raw[S], op);
     // (pin the half-converted operands here: the compiler otherwise sinks the conversion
     // behind the barrier, next to the LDS writes of part 2, and the two parts are uneven)
@@ -387,23 +363,14 @@ __device__ __forceinline__ void produce(const BlockArgs& A, const SegTab& tab, C
   };
   auto part2 = [&](auto slot) {
     constexpr int S = decltype(slot)::value;
-#ifdef MSMD_WGRAD_BLOCK_DBG
-    if (A.dbg & (64 | 128)) return;
-#endif
     // (and keep the second half of the conversion on this side of the barrier)
 #pragma unroll
     for (int e = 4; e < 8; ++e)
 #pragma unroll
       for (int a = 0; a < N; ++a) asm volatile("" : "+v"(raw[S][e][a]));
-#ifdef MSMD_WGRAD_BLOCK_DBG
-    if (!(A.dbg & 4))
-#endif
     split_rows<NP, N, 2, 4>(raw[S], op);
     if (wb_on) WB_MARK(1);
     u32x4* d = dst0 + ring_slot * slot_u;
-#ifdef MSMD_WGRAD_BLOCK_DBG
-    if (!(A.dbg & 32))
-#endif
 #pragma unroll
     for (int a = 0; a < N; ++a)
 #pragma unroll
@@ -776,12 +743,7 @@ int cu_count() {
     if (hipGetDevice(&dev) != hipSuccess) return 256;
     if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1)
       return 256;
-    // (MSMD_RESERVE_CUS: CUs left to the step's other queues, see spconv_split.hip)
-    const char* e = getenv("MSMD_RESERVE_CUS");
-    int r = e ? atoi(e) : 0;
-    r = r < 0 ? 0 : r > v / 2 ? v / 2 : r;
-    r &= ~7;                     // keep the grid a multiple of 8: the XCD-aware range mapping
-    return v - r;
+    return v;
   }();
   return n;
 }
@@ -854,8 +816,6 @@ int wgrad_block(const float* in_feat, int c_in, const float* d_out, int c_out,
   }
   A.segtab = segtab;
   A.nchunk = nchunk;
-  static const int dbg = [] { const char* e = getenv("MSMD_WGRAD_DBG"); return e ? atoi(e) : 0; }();
-  A.dbg = dbg;
   const int G = cu_count();
   if (np == 3) MSMD_LAUNCH(spconv_wgrad_block_kernel<3>, dim3(G), dim3(768), 0, st, A);
   else if (np == 2) MSMD_LAUNCH(spconv_wgrad_block_kernel<2>, dim3(G), dim3(768), 0, st, A);

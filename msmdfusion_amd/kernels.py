@@ -1423,7 +1423,7 @@ def wgrad_split_supported(c_in, c_out):
 
 
 # Rows per chunk of the wgrad kernel's row-chunk-major sequence; 0 (default) = offset-major.
-# Measured (MI355X, tools/wgrad_ablate.py, 128 x 128 at 89.7 k rows): offset-major 263 us;
+# Measured (MI355X, tools/wgrad_ablate.py since pruned, 128 x 128 at 89.7 k rows): offset-major 263 us;
 # 8192 / 4096 / 2048 / 1024-row chunks 270 / 278 / 308 / 367 us -- every (chunk, offset)
 # boundary is another 64 KB partial slot for the reduction pass to read, and the main kernel
 # does not get faster with its rows in L2: it is not the bandwidth-bound kernel the PMC

@@ -2,7 +2,6 @@
 against the CPU oracle on the same seeded inputs.  Integer results (voxel
 indices, rulebooks, set operations, FPS / ball query) must match bit for bit;
 fp32 features within 1e-4 (BASELINE.json north_star)."""
-import os
 
 import numpy as np
 import pytest
@@ -1197,8 +1196,8 @@ def test_rulebook_tiling_one_call(dev, n, kvol):
     """msmd_rulebook_tiling against row_mask_order + permute_cols (the torch-side
     route): a permutation of the rows, the table in that order, and tiles that cost
     the same (ties between equal keys may be broken differently).  The one-call tiling
-    keeps the tiles in mask order (stream-K balances them wherever they lie); the
-    heaviest-first re-sequencing of whole tiles is MSMD_TILE_LPT=1 / tile_lpt=True."""
+    keeps the tiles in mask order (stream-K balances them wherever they lie), so the
+    reference is row_mask_order without the heaviest-first re-sequencing of whole tiles."""
     from msmdfusion_amd import kernels as K
     g = torch.Generator().manual_seed(n + kvol)
     nbr = torch.where(torch.rand(kvol, n, generator=g) < 0.35,
@@ -1206,7 +1205,7 @@ def test_rulebook_tiling_one_call(dev, n, kvol):
     order, tiled = K.rulebook_tiling(nbr)
     assert sorted(order.cpu().tolist()) == list(range(n))
     assert torch.equal(tiled, K.permute_cols(nbr, order))
-    ref = K.row_mask_order(nbr, tile_lpt=os.environ.get("MSMD_TILE_LPT", "0") == "1")
+    ref = K.row_mask_order(nbr, tile_lpt=False)
 
     def unions(o):      # offsets each 128-row tile walks
         m = (nbr[:, o.long()] >= 0)

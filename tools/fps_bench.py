@@ -4,8 +4,7 @@ coordinates of synthetic virtual points at stage 0 (0.075 m) and stage 1
 (0.15 m), in first-touch order (what hard voxelization emits) and shuffled (the
 pruned kernel's worst case), and checks every result against the oracle.
 
-    python tools/fps_bench.py            # pruned kernel (default)
-    MSMD_FPS_PRUNE=0 python tools/fps_bench.py
+    python tools/fps_bench.py
 """
 import os
 import sys
@@ -30,7 +29,6 @@ def voxel_coords(seed, scale, n_pts):
 
 def main():
     dev = torch.device("cuda:0")
-    mode = "plain" if os.environ.get("MSMD_FPS_PRUNE") == "0" else "pruned"
     for name, scale, n_pts in [("stage0", 1, 50000), ("stage0-big", 1, 56000), ("stage1", 2, 50000)]:
         a, b = voxel_coords(0, scale, n_pts), voxel_coords(1, scale, n_pts)
         n = min(a.shape[0], b.shape[0])
@@ -50,8 +48,8 @@ def main():
                 K.furthest_point_sample(t, 2048)
                 torch.cuda.synchronize()
                 ts.append((time.perf_counter() - t0) * 1e3)
-            print("%-6s %-10s %-11s n=%5d x2  %.3f ms  (%.2f us/round)  oracle-exact=%s"
-                  % (mode, name, order, n, min(ts), min(ts) / 2047 * 1e3, ok), flush=True)
+            print("%-10s %-11s n=%5d x2  %.3f ms  (%.2f us/round)  oracle-exact=%s"
+                  % (name, order, n, min(ts), min(ts) / 2047 * 1e3, ok), flush=True)
 
 
 if __name__ == "__main__":
