@@ -1092,6 +1092,50 @@ int msmd_gaussian_focal_f32(const float* logits, const float* target, int64_t n,
                             float* sums /* [2] */, void* workspace,
                             size_t workspace_bytes, msmd_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * p1  Pillar feature net: decoration + Linear + BatchNorm1d + ReLU + max / mean over the slots
+ * replaces: PillarFeatureNet.forward  mmdet3d/models/voxel_encoders/pillar_encoder.py:91-150
+ *           PFNLayer.forward          mmdet3d/models/voxel_encoders/utils.py:191-227
+ * (one PFN layer; the encoder has no gradient to its input).
+ * voxels[N, M, C] float32 (the padded table of hard voxelization, never written), num_points[N]
+ * (>= 1, may exceed M), coors[N, 4] (batch, z, y, x).  flags: 1 with_cluster_center,
+ * 2 with_voxel_center, 4 with_distance, 8 legacy.  Decorated row of slot m (K = C + 3 + 2 + 1
+ * channels for the flags set, in this order): raw channels (legacy with voxel centre: channels
+ * 0, 1 hold x - cx, y - cy, as the reference's in-place view leaves them), xyz minus
+ * (sum over all M slots) / num_points, x - (coors[3] vx + x_offset), y - (coors[2] vy +
+ * y_offset), |xyz|; rows with m >= num_points are zero rows (and count in the statistics).
+ * Built shapes: K <= 16, U <= 128, M <= 64, C >= 3 (else MSMD_ERR_UNSUPPORTED).  N == 0: ok,
+ * nothing is launched.  All sums: fp64 per workgroup, workgroups added in order (no atomics). */
+size_t msmd_pillar_workspace_bytes(int num_pillars, int max_points, int out_channels);
+/* moments[0..16) = column sums s of the decorated rows, moments[16 + 16 i + j] = G[i][j] =
+ * sum f_i f_j over all N * M rows (entries past K are 0): the batch statistics of W f follow
+ * as mean = W s / n, var = w^T (G / n - s s^T / n^2) w. */
+int msmd_pillar_moments_f32(const float* voxels, const int32_t* num_points,
+                            const int32_t* coors, int num_pillars, int max_points,
+                            int num_features, int flags, float vx, float vy, float x_offset,
+                            float y_offset, double* moments /* [272] */, void* workspace,
+                            size_t workspace_bytes, msmd_stream_t stream);
+/* out[n, u] = max over the M slots (mode_max) or (sum over the M slots) / num_points of
+ * relu(scale[u] * (weight[u] . f) + shift[u]); argmax[n, u] (mode_max): the smallest slot
+ * attaining the maximum. */
+int msmd_pillar_pfn_fwd_f32(const float* voxels, const int32_t* num_points,
+                            const int32_t* coors, int num_pillars, int max_points,
+                            int num_features, int flags, float vx, float vy, float x_offset,
+                            float y_offset, const float* weight /* [U, K] */,
+                            const float* scale /* [U] */, const float* shift /* [U] */,
+                            int out_channels, int mode_max, float* out /* [N, U] */,
+                            uint8_t* argmax /* [N, U] or NULL */, msmd_stream_t stream);
+/* g = grad_out [y > 0] at the argmax slot (mode_max) or grad_out / num_points [y > 0] at every
+ * slot; sums[u * 17 + k] = sum g f_k (k < 16), sums[u * 17 + 16] = sum g. */
+int msmd_pillar_pfn_bwd_f32(const float* voxels, const int32_t* num_points,
+                            const int32_t* coors, int num_pillars, int max_points,
+                            int num_features, int flags, float vx, float vy, float x_offset,
+                            float y_offset, const float* weight, const float* scale,
+                            const float* shift, int out_channels, int mode_max,
+                            const float* grad_out /* [N, U] */, const uint8_t* argmax,
+                            double* sums /* [U, 17] */, void* workspace,
+                            size_t workspace_bytes, msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,65 @@ MSMDFUSION_LC = dict(
                        "norm": dict(decay_mult=0.)})),
     freeze_lidar_components=True)
 
+# configs/transfusion_nusc_pillar_L.py:150-242: the whole `model` dict (head, train_cfg and
+# test_cfg included; equality pinned by tests/golden/reference_pillar_config.json)
+PILLAR_POINT_CLOUD_RANGE = [-51.2, -51.2, -5.0, 51.2, 51.2, 3.0]
+PILLAR_VOXEL_SIZE = [0.2, 0.2, 8]
+_PILLAR_OUT_SIZE_FACTOR = 4
+_PILLAR_BN = dict(type="BN", eps=0.001, momentum=0.01)
+
+TRANSFUSION_PILLAR_L = dict(
+    model=dict(
+        type="TransFusionDetector",
+        pts_voxel_layer=dict(max_num_points=20, voxel_size=PILLAR_VOXEL_SIZE,
+                             max_voxels=(30000, 60000),
+                             point_cloud_range=PILLAR_POINT_CLOUD_RANGE),
+        pts_voxel_encoder=dict(type="PillarFeatureNet", in_channels=5, feat_channels=[64],
+                               with_distance=False, voxel_size=PILLAR_VOXEL_SIZE,
+                               norm_cfg=dict(type="BN1d", eps=0.001, momentum=0.01),
+                               point_cloud_range=PILLAR_POINT_CLOUD_RANGE),
+        pts_middle_encoder=dict(type="PointPillarsScatter", in_channels=64,
+                                output_shape=(512, 512)),
+        pts_backbone=dict(type="SECOND", in_channels=64, out_channels=[64, 128, 256],
+                          layer_nums=[3, 5, 5], layer_strides=[2, 2, 2], norm_cfg=_PILLAR_BN,
+                          conv_cfg=dict(type="Conv2d", bias=False)),
+        pts_neck=dict(type="SECONDFPN", in_channels=[64, 128, 256], out_channels=[128, 128, 128],
+                      upsample_strides=[0.5, 1, 2], norm_cfg=_PILLAR_BN,
+                      upsample_cfg=dict(type="deconv", bias=False), use_conv_for_no_stride=True),
+        pts_bbox_head=dict(
+            type="TransFusionHead", num_proposals=200, auxiliary=True, in_channels=128 * 3,
+            hidden_channel=128, num_classes=10, num_decoder_layers=1, num_heads=8,
+            learnable_query_pos=False, initialize_by_heatmap=True, nms_kernel_size=3,
+            ffn_channel=256, dropout=0.1, bn_momentum=0.1, activation="relu",
+            common_heads=dict(center=(2, 2), height=(1, 2), dim=(3, 2), rot=(2, 2), vel=(2, 2)),
+            bbox_coder=dict(type="TransFusionBBoxCoder", pc_range=PILLAR_POINT_CLOUD_RANGE[:2],
+                            voxel_size=PILLAR_VOXEL_SIZE[:2],
+                            out_size_factor=_PILLAR_OUT_SIZE_FACTOR,
+                            post_center_range=[-61.2, -61.2, -10.0, 61.2, 61.2, 10.0],
+                            score_threshold=0.0, code_size=10),
+            loss_cls=dict(type="FocalLoss", use_sigmoid=True, gamma=2, alpha=0.25,
+                          reduction="mean", loss_weight=1.0),
+            loss_bbox=dict(type="L1Loss", reduction="mean", loss_weight=0.25),
+            loss_heatmap=dict(type="GaussianFocalLoss", reduction="mean", loss_weight=1.0)),
+        train_cfg=dict(pts=dict(
+            dataset="nuScenes",
+            assigner=dict(type="HungarianAssigner3D",
+                          iou_calculator=dict(type="BboxOverlaps3D", coordinate="lidar"),
+                          cls_cost=dict(type="FocalLossCost", gamma=2, alpha=0.25, weight=0.15),
+                          reg_cost=dict(type="BBoxBEVL1Cost", weight=0.25),
+                          iou_cost=dict(type="IoU3DCost", weight=0.25)),
+            pos_weight=-1, gaussian_overlap=0.1, min_radius=2, grid_size=[512, 512, 1],
+            voxel_size=PILLAR_VOXEL_SIZE, out_size_factor=_PILLAR_OUT_SIZE_FACTOR,
+            code_weights=[1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 0.2, 0.2],
+            point_cloud_range=PILLAR_POINT_CLOUD_RANGE)),
+        test_cfg=dict(pts=dict(dataset="nuScenes", grid_size=[512, 512, 1],
+                               out_size_factor=_PILLAR_OUT_SIZE_FACTOR,
+                               pc_range=PILLAR_POINT_CLOUD_RANGE[0:2],
+                               voxel_size=PILLAR_VOXEL_SIZE[:2], nms_type=None))),
+    samples_per_gpu=2, point_cloud_range=PILLAR_POINT_CLOUD_RANGE, voxel_size=PILLAR_VOXEL_SIZE,
+    optimizer=dict(type="AdamW", lr=0.0001, weight_decay=0.01),
+    freeze_lidar_components=False)
+
 
 def build_hot_path(cfg):
     """(Voxelization, voxel encoder, SparseEncoder, multimodal encoder | None) from one of
@@ -134,8 +193,15 @@ def build_bev_tail(cfg, compute_dtype=None, rows=True):
 def build_head(cfg=None, rows=False):
     """pts_bbox_head of configs/MSMDFusion_nusc_voxel_LC.py:207-241 with its test_cfg
     (:260-268) and train_cfg (:242-259): TransFusionHead, LiDAR branch (msmdfusion_amd/head.py,
-    head_loss.py)."""
+    head_loss.py).  cfg: one of the dicts above; one whose model carries `pts_bbox_head`,
+    `train_cfg` and `test_cfg` (TRANSFUSION_PILLAR_L) gets its own head."""
     from .head import TransFusionHead
+    if cfg is not None and "pts_bbox_head" in cfg.get("model", {}):
+        # a config that carries its own head (TRANSFUSION_PILLAR_L): its dicts, not the LC ones
+        m = cfg["model"]
+        args = {k: v for k, v in m["pts_bbox_head"].items() if k != "type"}
+        return TransFusionHead(test_cfg=dict(m["test_cfg"]["pts"]),
+                               train_cfg=dict(m["train_cfg"]["pts"]), rows=rows, **args)
     args = {k: v for k, v in _PTS_BBOX_HEAD.items() if k != "type"}
     return TransFusionHead(test_cfg=dict(_TEST_CFG_PTS), train_cfg=dict(_TRAIN_CFG_PTS), rows=rows,
                            **args)

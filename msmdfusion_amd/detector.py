@@ -61,7 +61,9 @@ def _build_head(cfg, train_cfg, test_cfg, rows):
 @DETECTORS.register_module()
 class TransFusionDetector(nn.Module):
     """LiDAR-only detector (configs/transfusion_nusc_voxel_L.py): voxelize -> HardSimpleVFE ->
-    SparseEncoder -> SECOND -> SECONDFPN -> TransFusionHead.
+    SparseEncoder -> SECOND -> SECONDFPN -> TransFusionHead; and the pillar form of
+    configs/transfusion_nusc_pillar_L.py: voxelize -> PillarFeatureNet (on the padded pillar
+    table) -> PointPillarsScatter -> the same tail.
 
     A `pts_voxel_layer` with max_num_points=-1 (or max_voxels=-1) selects dynamic
     voxelization (DynamicVoxelNet.voxelize, dynamic_voxelnet.py:46-71) with a dynamic voxel
@@ -113,7 +115,24 @@ class TransFusionDetector(nn.Module):
     def dynamic_voxelization(self):
         return self.pts_voxel_layer.max_num_points == -1 or -1 in self.pts_voxel_layer.max_voxels
 
+    @property
+    def voxel_table_encoder(self):
+        """The voxel encoder reads the padded [N, max_points, C] table (PillarFeatureNet),
+        not the per-voxel means: it says so itself (`takes_voxel_table`)."""
+        return bool(getattr(self.pts_voxel_encoder, "takes_voxel_table", False))
+
     # ---- the path ----------------------------------------------------------------------
+    @torch.no_grad()
+    def voxelize_table(self, points):
+        """mvx_two_stage.py:voxelize: hard voxelization per sample, batch id prepended, the
+        table kept.  -> (voxels[N, max_points, C], num_points[N], coors[N, 4])"""
+        voxels, nums, coors = [], [], []
+        for b, (v, c, n) in enumerate(self.pts_voxel_layer.forward_batch(points, fused_mean=False)):
+            voxels.append(v)
+            nums.append(n)
+            coors.append(nn.functional.pad(c, (1, 0), mode="constant", value=b))
+        return torch.cat(voxels, 0), torch.cat(nums, 0), torch.cat(coors, 0)
+
     @torch.no_grad()
     def voxelize_dynamic(self, points):
         """dynamic_voxelnet.py:46-71: per-sample dynamic voxelization, batch id prepended.
@@ -139,6 +158,8 @@ class TransFusionDetector(nn.Module):
         step ahead.  Dynamic voxelization: the points, their coordinates and the scatter
         index (whose voxel rows the encoder's rulebooks are built on) take the place of the
         voxel features."""
+        if not hasattr(self.pts_middle_encoder, "plan"):
+            return self._prepare_pillars(points)
         if self.dynamic_voxelization:
             from .dynamic_scatter import scatter_index
             pts, coors = self.voxelize_dynamic(points)
@@ -149,8 +170,31 @@ class TransFusionDetector(nn.Module):
         planned, _ = self.pts_middle_encoder.plan(coors, len(points))
         return feats, coors, planned
 
+    def _prepare_pillars(self, points):
+        """prepare() in front of a middle encoder with nothing to plan (PointPillarsScatter):
+        the pillar table, or under dynamic voxelization the points and their scatter index."""
+        if self.dynamic_voxelization:
+            from .dynamic_scatter import scatter_index
+            pts, coors = self.voxelize_dynamic(points)
+            index = scatter_index(coors.contiguous())
+            return (pts, coors, index), index.voxel_coors, None
+        if not self.voxel_table_encoder:
+            raise NotImplementedError("%s in front of %s is not built"
+                                      % (type(self.pts_voxel_encoder).__name__,
+                                         type(self.pts_middle_encoder).__name__))
+        voxels, num_points, coors = self.voxelize_table(points)
+        return (voxels, num_points), coors, None
+
     def extract_sparse_feat(self, points, prepared=None):
         feats, coors, planned = prepared if prepared is not None else self.prepare(points)
+        if not hasattr(self.pts_middle_encoder, "plan"):
+            if self.dynamic_voxelization:
+                pts, pts_coors, index = feats
+                feats, coors = self.pts_voxel_encoder(pts, pts_coors, index=index)
+            else:
+                voxels, num_points = feats
+                feats = self.pts_voxel_encoder(voxels, num_points, coors)
+            return self.pts_middle_encoder(feats, coors, len(points))
         if self.dynamic_voxelization:
             pts, pts_coors, index = feats
             feats, coors = self.pts_voxel_encoder(pts, pts_coors, index=index)

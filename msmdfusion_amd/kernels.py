@@ -2239,3 +2239,98 @@ def rows_linear(x, weight, bias=None, relu=False, x_tail=None):
     without materialising the concatenation."""
     _need_cuda(x, weight)
     return _RowsLinear.apply(x, x_tail, weight, bias, relu)
+
+
+# ------------------------------------------------------------------ pillar feature net
+PILLAR_MAX_K, PILLAR_MAX_U, PILLAR_MAX_M = 16, 128, 64
+
+
+class PillarGeometry:
+    """The decoration a PillarFeatureNet applies (csrc/pillar.hip): flags, pillar size and the
+    centre offsets, as the float32 values the reference's tensor arithmetic rounds them to."""
+
+    def __init__(self, with_cluster_center, with_voxel_center, with_distance, legacy, vx, vy,
+                 x_offset, y_offset):
+        self.flags = (1 if with_cluster_center else 0) | (2 if with_voxel_center else 0) | \
+            (4 if with_distance else 0) | (8 if legacy else 0)
+        self.vx, self.vy = float(vx), float(vy)
+        self.x_offset, self.y_offset = float(x_offset), float(y_offset)
+
+    def decorated(self, c):
+        return c + 3 * (self.flags & 1) + (self.flags & 2) + ((self.flags & 4) >> 2)
+
+    def args(self):
+        return self.flags, self.vx, self.vy, self.x_offset, self.y_offset
+
+
+def pillar_supported(m, c, k, u):
+    return 1 <= m <= PILLAR_MAX_M and c >= 3 and k <= PILLAR_MAX_K and 1 <= u <= PILLAR_MAX_U
+
+
+def _pillar_inputs(voxels, num_points, coors):
+    _need_cuda(voxels, num_points, coors)
+    _need_dtype(voxels, torch.float32, "voxels")
+    _need_dtype(num_points, torch.int32, "num_points")
+    _need_dtype(coors, torch.int32, "coors")
+    if voxels.dim() != 3 or not voxels.is_contiguous():
+        raise ValueError("voxels must be a contiguous [N, M, C] table, got %s" % (tuple(voxels.shape),))
+    n = voxels.shape[0]
+    if tuple(num_points.shape) != (n,) or tuple(coors.shape) != (n, 4) or \
+            not num_points.is_contiguous() or not coors.is_contiguous():
+        raise ValueError("num_points must be [N] and coors [N, 4] (batch, z, y, x), contiguous")
+    return n, int(voxels.shape[1]), int(voxels.shape[2])
+
+
+def pillar_moments(voxels, num_points, coors, geom):
+    """-> (s[K], G[K, K]) float64: column sums and Gram matrix of the decorated rows of all
+    N * M slots."""
+    n, m, c = _pillar_inputs(voxels, num_points, coors)
+    k = geom.decorated(c)
+    dev = voxels.device
+    mom = torch.zeros(272, dtype=torch.float64, device=dev) if n == 0 else \
+        torch.empty(272, dtype=torch.float64, device=dev)
+    nbytes = lib.msmd_pillar_workspace_bytes(n, m, 1)
+    ws = _ws(nbytes, dev)
+    check(lib.msmd_pillar_moments_f32(_p(voxels), _p(num_points), _p(coors), n, m, c,
+                                      *geom.args(), _p(mom), _p(ws), nbytes, _stream()),
+          "msmd_pillar_moments_f32")
+    return mom[:k], mom[16:].view(16, 16)[:k, :k]
+
+
+def pillar_pfn_forward(voxels, num_points, coors, geom, weight, scale, shift, mode):
+    """-> (out[N, U], argmax[N, U] uint8 | None)."""
+    n, m, c = _pillar_inputs(voxels, num_points, coors)
+    _need_cuda(weight, scale, shift)
+    u = int(weight.shape[0])
+    if tuple(weight.shape) != (u, geom.decorated(c)) or not weight.is_contiguous():
+        raise ValueError("weight must be a contiguous [U, K=%d] matrix, got %s"
+                         % (geom.decorated(c), tuple(weight.shape)))
+    mode_max = {"max": 1, "avg": 0}[mode]
+    out = torch.empty((n, u), dtype=torch.float32, device=voxels.device)
+    arg = torch.empty((n, u), dtype=torch.uint8, device=voxels.device) if mode_max else None
+    check(lib.msmd_pillar_pfn_fwd_f32(_p(voxels), _p(num_points), _p(coors), n, m, c,
+                                      *geom.args(), _p(weight), _p(scale), _p(shift), u, mode_max,
+                                      _p(out), _p(arg), _stream()), "msmd_pillar_pfn_fwd_f32")
+    return out, arg
+
+
+def pillar_pfn_backward(voxels, num_points, coors, geom, weight, scale, shift, mode, grad_out,
+                        argmax):
+    """-> (A[U, K], sg[U]) float64: sum g f and sum g over the slots the gradient reaches."""
+    n, m, c = _pillar_inputs(voxels, num_points, coors)
+    _need_cuda(weight, scale, shift, grad_out, argmax)
+    u, k = int(weight.shape[0]), geom.decorated(c)
+    _need_dtype(grad_out, torch.float32, "grad_out")
+    if tuple(grad_out.shape) != (n, u) or not grad_out.is_contiguous():
+        raise ValueError("grad_out must be a contiguous [N, U] tensor")
+    dev = voxels.device
+    sums = torch.zeros((u, 17), dtype=torch.float64, device=dev) if n == 0 else \
+        torch.empty((u, 17), dtype=torch.float64, device=dev)
+    nbytes = lib.msmd_pillar_workspace_bytes(n, m, u)
+    ws = _ws(nbytes, dev)
+    mode_max = {"max": 1, "avg": 0}[mode]
+    check(lib.msmd_pillar_pfn_bwd_f32(_p(voxels), _p(num_points), _p(coors), n, m, c,
+                                      *geom.args(), _p(weight), _p(scale), _p(shift), u, mode_max,
+                                      _p(grad_out), _p(argmax), _p(sums), _p(ws), nbytes,
+                                      _stream()), "msmd_pillar_pfn_bwd_f32")
+    return sums[:, :k], sums[:, 16]
