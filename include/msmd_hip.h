@@ -45,7 +45,7 @@ const char* msmd_status_string(int status);
 /* hipGetErrorString() of the launch that made the calling thread's most recent
  * MSMD_ERR_LAUNCH. */
 const char* msmd_last_launch_error(void);
-/* ABI version: bumped whenever a signature below changes. */
+/* ABI version: bumped whenever a signature below changes or is added (2: the n1 section). */
 int msmd_abi_version(void);
 /* 1 when a gfx950 device is visible to this process, else 0 (host call). */
 int msmd_device_ok(void);
@@ -1135,6 +1135,75 @@ int msmd_pillar_pfn_bwd_f32(const float* voxels, const int32_t* num_points,
                             const float* grad_out /* [N, U] */, const uint8_t* argmax,
                             double* sums /* [U, 17] */, void* workspace,
                             size_t workspace_bytes, msmd_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
+ * n1  PointNet++ op family (csrc/pointnet.hip)
+ * replaces: gather_points_ext.gather_points_wrapper / gather_points_grad_wrapper
+ *           mmdet3d/ops/gather_points/src/gather_points_cuda.cu:9-94
+ *           group_points_ext.forward / backward
+ *           mmdet3d/ops/group_points/src/group_points_cuda.cu:12-101
+ *           interpolate_ext.three_nn_wrapper
+ *           mmdet3d/ops/interpolate/src/three_nn_cuda.cu:11-89
+ *           interpolate_ext.three_interpolate_wrapper / three_interpolate_grad_wrapper
+ *           mmdet3d/ops/interpolate/src/three_interpolate_cuda.cu:11-108
+ *           knn_ext.knn_wrapper  mmdet3d/ops/knn/src/knn_cuda.cu:26-268
+ *           furthest_point_sample_ext.furthest_point_sampling_with_dist_wrapper
+ *           mmdet3d/ops/furthest_point_sample/src/furthest_point_sample_cuda.cu:214-400
+ * Features are (B, C, N) channel-major, xyz (B, N, 3), indices int32.  An index outside
+ * [0, N) reads as 0 in the forward ops and is left out of the backward (the reference reads
+ * and adds out of bounds).  B <= 65535, C <= 4 * 65535.
+ * ------------------------------------------------------------------------ */
+/* out[b, c, j] = features[b, c, idx[b, j]] */
+int msmd_gather_points_f32(const float* features /* [b,c,n] */, const int32_t* idx /* [b,npoint] */,
+                           int b, int c, int n, int npoint, float* out /* [b,c,npoint] */,
+                           msmd_stream_t stream);
+/* out[b, c, p, s] = features[b, c, idx[b, p, s]]; npoint * nsample < 2^31 */
+int msmd_group_points_f32(const float* features /* [b,c,n] */,
+                          const int32_t* idx /* [b,npoint,nsample] */, int b, int c, int n,
+                          int npoint, int nsample, float* out /* [b,c,npoint,nsample] */,
+                          msmd_stream_t stream);
+/* The three nearest known points of every unknown point: float32
+ * d = (dx*dx + dy*dy) + dz*dz, strict <, lowest index on ties; dist2 is the SQUARED distance
+ * (three_nn.py takes the root).  m < 3: the missing entries are index 0, distance +inf. */
+int msmd_three_nn_f32(const float* unknown /* [b,n,3] */, const float* known /* [b,m,3] */,
+                      int b, int n, int m, float* dist2 /* [b,n,3] */, int32_t* idx /* [b,n,3] */,
+                      msmd_stream_t stream);
+/* out[b, c, j] = (w0 f[i0] + w1 f[i1]) + w2 f[i2], i = idx[b, j, :], w = weight[b, j, :] */
+int msmd_three_interpolate_f32(const float* features /* [b,c,m] */,
+                               const int32_t* idx /* [b,n,3] */,
+                               const float* weight /* [b,n,3] */, int b, int c, int m, int n,
+                               float* out /* [b,c,n] */, msmd_stream_t stream);
+/* idx[b, j, p] = the j-th nearest of the n points to centre p, 0-based, ordered by
+ * (d2, index) ascending (the order the reference's stable insertion sort leaves); d2 as in
+ * three_nn -- the reference's chained ssd += tmp*tmp may be contracted by its compiler, so d2
+ * itself is not claimed bit-equal.  No [n x npoint] matrix is written.  Built for
+ * 1 <= k <= 128: k > 128 returns MSMD_ERR_UNSUPPORTED, k < 1 or k > n MSMD_ERR_INVALID_ARG. */
+int msmd_knn_f32(const float* xyz /* [b,n,3] */, const float* center_xyz /* [b,npoint,3] */,
+                 int b, int n, int npoint, int k, int64_t* idx /* [b,k,npoint] */,
+                 msmd_stream_t stream);
+/* Furthest point sampling on a distance matrix: idx[b, 0] = 0, the running minimum is taken
+ * against row `old`; the reference block reduction's tie order, as msmd_furthest_point_sample.
+ * n < 2^21. */
+int msmd_furthest_point_sample_with_dist(const float* dist /* [b,n,n] */, int b, int n, int m,
+                                         float* temp /* [b,n] scratch */,
+                                         int32_t* idx /* [b,m] */, msmd_stream_t stream);
+/* By-source inverse of an index tensor, for the backward of the three ops above: the
+ * destinations j in [0, m) of batch element b whose idx[b, j] == s are
+ * dest[src_start[b*n + s] .. src_start[b*n + s + 1]), in ASCENDING j (stable radix sort; no
+ * dependence on atomic arrival order).  b*m and b*n < 2^31. */
+size_t msmd_point_inverse_index_workspace_bytes(int b, int m);
+int msmd_point_inverse_index(const int32_t* idx /* [b,m] */, int b, int n, int m,
+                             int32_t* src_start /* [b*n+1] */, int32_t* dest /* [b*m] */,
+                             void* workspace, size_t workspace_bytes, msmd_stream_t stream);
+/* grad_in[b, c, s] (+)= sum over the source's destinations j, in list order, float32 with a
+ * Kahan compensation term (y = term - comp; sum = acc + y; comp = (sum - acc) - y), of
+ * weight[b, j] * grad_out[b, c, j / dest_per_out] (weight NULL: 1).  dest_per_out = 1 for
+ * gather / group, 3 for three_interpolate (destinations are its (point, slot) pairs);
+ * grad_out is [b, c, m / dest_per_out].  No float atomics: bitwise reproducible. */
+int msmd_point_scatter_bwd_f32(const float* grad_out, const float* weight /* [b,m] or NULL */,
+                               const int32_t* src_start, const int32_t* dest, int b, int c,
+                               int n, int m, int dest_per_out, int accumulate,
+                               float* grad_in /* [b,c,n] */, msmd_stream_t stream);
 
 #ifdef __cplusplus
 }

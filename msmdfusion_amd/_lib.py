@@ -181,6 +181,15 @@ SIGNATURES = {
                                      _i, _vp, _vp, _vp]),
     "msmd_pillar_pfn_bwd_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _i,
                                      _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "msmd_gather_points_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "msmd_group_points_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "msmd_three_nn_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "msmd_three_interpolate_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "msmd_knn_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "msmd_furthest_point_sample_with_dist": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "msmd_point_inverse_index_workspace_bytes": (_sz, [_i, _i]),
+    "msmd_point_inverse_index": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "msmd_point_scatter_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
@@ -188,7 +197,7 @@ for _name, (_res, _args) in SIGNATURES.items():
     _fn.restype = _res
     _fn.argtypes = _args
 
-ABI_VERSION = 1
+ABI_VERSION = 2
 if lib.msmd_abi_version() != ABI_VERSION:
     raise RuntimeError("libmsmd_hip.so ABI version mismatch: rebuild msmdfusion_amd/csrc")
 

@@ -9,6 +9,7 @@
 // (furthest_point_sample_cuda.cu:17-23,55-137): among equal distances the
 // point with the smallest (k mod block, k) wins, block = opt_n_threads(n).
 #include "common.hpp"
+#include "fps_order.hpp"
 
 #include <math.h>
 
@@ -103,15 +104,12 @@ __global__ __launch_bounds__(1024) void fps_kernel(const float* __restrict__ xyz
   // reference block size opt_n_threads(n): largest power of two <= n, max 1024
   // (furthest_point_sample_cuda.cu:11-15)
   const int bs_shift = min(31 - __clz(n), 10);
-  const int bs_ref = 1 << bs_shift;
   // tie rank of point k: the reference's shared-memory tree keeps the LOWER slot
   // of each (t, t+s) pair, s = bs/2 .. 1, so between two thread ids the one
   // whose lowest differing bit is 0 wins: order by the bit-reversed thread id
   // (k mod bs), then by k div bs (the strided scan keeps its first maximum).
-  auto tie_rank = [&](int k) -> uint32_t {
-    uint32_t rev = bs_shift ? (__brev((uint32_t)(k & (bs_ref - 1))) >> (32 - bs_shift)) : 0u;
-    return (rev << 21) | (uint32_t)(k >> bs_shift);
-  };
+  // (the formula lives in fps_order.hpp: the distance-matrix form in pointnet.hip shares it)
+  auto tie_rank = [&](int k) -> uint32_t { return fps_tie_rank(k, bs_shift); };
   float px[P], py[P], pz[P], pd[P];
   if (PPT > 0) {
 #pragma unroll
@@ -683,7 +681,7 @@ MSMD_EXPORT const char* msmd_status_string(int status) {
 MSMD_EXPORT const char* msmd_last_launch_error(void) {
   return hipGetErrorString((hipError_t)g_last_detail);
 }
-MSMD_EXPORT int msmd_abi_version(void) { return 1; }
+MSMD_EXPORT int msmd_abi_version(void) { return 2; }
 MSMD_EXPORT int msmd_device_ok(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return 0;

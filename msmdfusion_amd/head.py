@@ -48,15 +48,16 @@ class ConvModule(nn.Module):
     norm."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias="auto",
-                 conv="Conv1d", norm="BN1d"):
+                 conv="Conv1d", norm="BN1d", norm_kwargs=None):
         super().__init__()
-        conv_cls = {"Conv1d": Conv1d, "Conv2d": nn.Conv2d}[conv]
+        conv_cls = conv if isinstance(conv, type) else {"Conv1d": Conv1d, "Conv2d": nn.Conv2d}[conv]
         norm_cls = {"BN1d": nn.BatchNorm1d, "BN2d": nn.BatchNorm2d, None: None}[norm]
         if bias == "auto":
             bias = norm_cls is None
         self.conv = conv_cls(in_channels, out_channels, kernel_size, stride=stride,
                              padding=padding, bias=bool(bias))
-        self.bn = norm_cls(out_channels) if norm_cls is not None else None
+        # norm_kwargs: what a norm_cfg dict carries beside its type (eps, momentum)
+        self.bn = norm_cls(out_channels, **(norm_kwargs or {})) if norm_cls is not None else None
         self.activate = nn.ReLU(inplace=True)
 
     def forward(self, x):

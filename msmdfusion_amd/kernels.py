@@ -2182,6 +2182,183 @@ def nn_assign(group_idx, rep_nn, nq):
     return out
 
 
+# ------------------------------------------------------------------ PointNet++ op family (n1)
+KNN_MAX_K = 128      # csrc/pointnet.hip: kKnnMaxK
+
+
+def _need_f32(t, shape, what):
+    """A contiguous float32 tensor of the given shape (None = any size on that axis)."""
+    if t.dtype != torch.float32:
+        raise TypeError("%s must be float32, got %s" % (what, t.dtype))
+    if t.dim() != len(shape) or any(w is not None and int(v) != int(w)
+                                    for v, w in zip(t.shape, shape)):
+        raise ValueError("%s must be %s, got %s" % (what, list(shape), tuple(t.shape)))
+    return t.contiguous()
+
+
+def _need_i32(t, shape, what):
+    if t.dtype not in (torch.int32, torch.int64):
+        raise TypeError("%s must be an integer tensor, got %s" % (what, t.dtype))
+    if t.dim() != len(shape) or any(w is not None and int(v) != int(w)
+                                    for v, w in zip(t.shape, shape)):
+        raise ValueError("%s must be %s, got %s" % (what, list(shape), tuple(t.shape)))
+    return t.contiguous().int()
+
+
+def gather_points(features, indices, out=None):
+    """gather_points_ext.gather_points_wrapper: features (B, C, N), indices (B, M) ->
+    (B, C, M)."""
+    _need_cuda(features, indices, out)
+    f = _need_f32(features, (None, None, None), "features")
+    b, c, n = f.shape
+    idx = _need_i32(indices, (b, None), "indices")
+    m = idx.shape[1]
+    if out is None:
+        out = torch.empty((b, c, m), dtype=torch.float32, device=f.device)
+    check(lib.msmd_gather_points_f32(_p(f), _p(idx), b, c, n, m, _p(out), _stream()),
+          "msmd_gather_points_f32")
+    return out
+
+
+def group_points(features, indices, out=None):
+    """group_points_ext.forward: features (B, C, N), indices (B, npoint, nsample) ->
+    (B, C, npoint, nsample)."""
+    _need_cuda(features, indices, out)
+    f = _need_f32(features, (None, None, None), "features")
+    b, c, n = f.shape
+    idx = _need_i32(indices, (b, None, None), "indices")
+    npoint, nsample = idx.shape[1:]
+    if out is None:
+        out = torch.empty((b, c, npoint, nsample), dtype=torch.float32, device=f.device)
+    check(lib.msmd_group_points_f32(_p(f), _p(idx), b, c, n, npoint, nsample, _p(out),
+                                    _stream()), "msmd_group_points_f32")
+    return out
+
+
+def three_nn(unknown, known, dist2=None, idx=None):
+    """interpolate_ext.three_nn_wrapper: unknown (B, N, 3), known (B, M, 3) -> SQUARED
+    distances (B, N, 3) float32 and indices (B, N, 3) int32."""
+    _need_cuda(unknown, known, dist2, idx)
+    u = _need_f32(unknown, (None, None, 3), "unknown")
+    b, n, _ = u.shape
+    k = _need_f32(known, (b, None, 3), "known")
+    if dist2 is None:
+        dist2 = torch.empty((b, n, 3), dtype=torch.float32, device=u.device)
+    if idx is None:
+        idx = torch.empty((b, n, 3), dtype=torch.int32, device=u.device)
+    check(lib.msmd_three_nn_f32(_p(u), _p(k), b, n, k.shape[1], _p(dist2), _p(idx), _stream()),
+          "msmd_three_nn_f32")
+    return dist2, idx
+
+
+def three_interpolate(features, indices, weight, out=None):
+    """interpolate_ext.three_interpolate_wrapper: features (B, C, M), indices / weight
+    (B, N, 3) -> (B, C, N)."""
+    _need_cuda(features, indices, weight, out)
+    f = _need_f32(features, (None, None, None), "features")
+    b, c, m = f.shape
+    idx = _need_i32(indices, (b, None, 3), "indices")
+    n = idx.shape[1]
+    w = _need_f32(weight, (b, n, 3), "weight")
+    if out is None:
+        out = torch.empty((b, c, n), dtype=torch.float32, device=f.device)
+    check(lib.msmd_three_interpolate_f32(_p(f), _p(idx), _p(w), b, c, m, n, _p(out), _stream()),
+          "msmd_three_interpolate_f32")
+    return out
+
+
+def knn(k, xyz, center_xyz):
+    """The k nearest of xyz (B, N, 3) to every centre (B, npoint, 3): int64 (B, k, npoint),
+    0-based, ordered by (squared distance, index)."""
+    _need_cuda(xyz, center_xyz)
+    x = _need_f32(xyz, (None, None, 3), "xyz")
+    b, n, _ = x.shape
+    cx = _need_f32(center_xyz, (b, None, 3), "center_xyz")
+    k = int(k)
+    if k < 1:
+        raise ValueError("knn: k must be positive, got %d" % k)
+    if k > KNN_MAX_K:
+        raise ValueError("knn: k = %d, but the kernel is built for k <= %d" % (k, KNN_MAX_K))
+    if k > n:
+        raise ValueError("knn: k = %d neighbours asked of %d points" % (k, n))
+    npoint = cx.shape[1]
+    idx = torch.empty((b, k, npoint), dtype=torch.int64, device=x.device)
+    check(lib.msmd_knn_f32(_p(x), _p(cx), b, n, npoint, k, _p(idx), _stream()), "msmd_knn_f32")
+    return idx
+
+
+def furthest_point_sample_with_dist(points_dist, num_points, out=None):
+    """furthest_point_sample.py:41-66: points_dist (B, N, N) -> int32 (B, num_points)."""
+    _need_cuda(points_dist, out)
+    d = _need_f32(points_dist, (None, None, None), "points_dist")
+    b, n, n2 = d.shape
+    if n != n2:
+        raise ValueError("points_dist must be (B, N, N), got %s" % (tuple(d.shape),))
+    if out is None:
+        out = torch.empty((b, int(num_points)), dtype=torch.int32, device=d.device)
+    tmp = torch.empty((b, n), dtype=torch.float32, device=d.device)
+    check(lib.msmd_furthest_point_sample_with_dist(_p(d), b, n, int(num_points), _p(tmp), _p(out),
+                                                   _stream()),
+          "msmd_furthest_point_sample_with_dist")
+    return out
+
+
+class PointInverseIndex:
+    """By-source inverse of an index tensor (B, M) over N source points: the destinations of
+    source (b, s) are dest[src_start[b*N + s] : src_start[b*N + s + 1]], ascending."""
+    __slots__ = ("src_start", "dest", "b", "n", "m")
+
+    def __init__(self, src_start, dest, b, n, m):
+        self.src_start, self.dest, self.b, self.n, self.m = src_start, dest, b, n, m
+
+
+def point_inverse_index(indices, num_src):
+    """indices: (B, ...) integer tensor, flattened per batch element to (B, M)."""
+    _need_cuda(indices)
+    b = indices.shape[0]
+    m, n = (indices[0].numel() if b else 0), int(num_src)
+    idx = indices.contiguous().int().view(b, m)
+    nbytes = lib.msmd_point_inverse_index_workspace_bytes(b, m)
+    if nbytes == 0:
+        raise ValueError("point_inverse_index: %d x %d destinations do not fit 31 bits" % (b, m))
+    ws = _ws(nbytes, idx.device)
+    src_start = torch.empty((b * n + 1,), dtype=torch.int32, device=idx.device)
+    dest = torch.empty((max(b * m, 1),), dtype=torch.int32, device=idx.device)
+    check(lib.msmd_point_inverse_index(_p(idx), b, n, m, _p(src_start), _p(dest), _p(ws),
+                                       ws.numel(), _stream()), "msmd_point_inverse_index")
+    return PointInverseIndex(src_start, dest, b, n, m)
+
+
+def point_scatter_backward(grad_out, inverse, weight=None, dest_per_out=1, grad_in=None):
+    """grad_in[b, c, s] = sum over the source's destinations, in ascending position, of
+    weight * grad_out (float32, no atomics).  grad_out: (B, C, ...) with
+    M / dest_per_out positions per (b, c); grad_in given: added to (the shims' contract)."""
+    _need_cuda(grad_out, weight, grad_in)
+    if grad_out.dtype != torch.float32:
+        raise TypeError("grad_out must be float32, got %s" % grad_out.dtype)
+    b, n, m = inverse.b, inverse.n, inverse.m
+    g = grad_out.contiguous()
+    c = g.shape[1]
+    if g.shape[0] != b or g.numel() != b * c * (m // dest_per_out):
+        raise ValueError("grad_out %s does not match the index (B %d, %d destinations)"
+                         % (tuple(g.shape), b, m))
+    if weight is not None:
+        weight = _need_f32(weight.view(b, -1) if weight.is_contiguous() else
+                           weight.contiguous().view(b, -1), (b, m), "weight")
+    accumulate = grad_in is not None
+    if accumulate:
+        if tuple(grad_in.shape) != (b, c, n) or grad_in.dtype != torch.float32 or \
+                not grad_in.is_contiguous():
+            raise ValueError("grad_in must be a contiguous float32 (%d, %d, %d)" % (b, c, n))
+    else:
+        grad_in = torch.empty((b, c, n), dtype=torch.float32, device=g.device)
+    check(lib.msmd_point_scatter_bwd_f32(_p(g), _p(weight), _p(inverse.src_start),
+                                         _p(inverse.dest), b, c, n, m, int(dest_per_out),
+                                         int(accumulate), _p(grad_in), _stream()),
+          "msmd_point_scatter_bwd_f32")
+    return grad_in
+
+
 # ------------------------------------------------------------------ gate tables (a16)
 def rows_linear_supported(c_in, c_out):
     return bool(lib.msmd_rows_linear_supported(int(c_in), int(c_out)))

@@ -93,7 +93,8 @@ def build_norm_layer(cfg, num_features, postfix=""):
 def _register_hot_path():
     """Import the modules whose decorators fill the registries (mmdet3d does
     this from its package __init__)."""
-    from . import bev, multimodal_encoder, pillar_encoder, sparse_encoder, voxel_encoder  # noqa: F401
+    from . import (bev, multimodal_encoder, pillar_encoder, pointnet2, sparse_encoder,  # noqa: F401
+                   voxel_encoder)
     from .spconv import conv  # noqa: F401
 
 
