@@ -1093,6 +1093,48 @@ int msmd_gaussian_focal_f32(const float* logits, const float* target, int64_t n,
                             size_t workspace_bytes, msmd_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * n2  iou3d: BEV IoU and rotated / axis-aligned / circle NMS, batched over segments
+ * replaces: iou3d_cuda.boxes_iou_bev_gpu  (mmdet3d/ops/iou3d/src/iou3d.cpp:100-126, kernel
+ *           iou3d_kernel.cu:244-281)
+ *           iou3d_cuda.nms_gpu / nms_normal_gpu  (iou3d.cpp:128-232: mask kernel
+ *           iou3d_kernel.cu:283-419, device -> host copy of the mask, host reduction)
+ *           circle_nms  (mmdet3d/core/post_processing/box3d_nms.py:141-181, a numba loop
+ *           over host copies of the boxes)
+ * and their per-task, per-sample call sites CenterHead.get_task_detections
+ * (models/dense_heads/centerpoint_head.py:737-852) and TransFusionHead.get_bboxes
+ * (transfusion_head.py:1334-1367).
+ * ------------------------------------------------------------------------ */
+/* IoU of rotated BEV rectangles (x1, y1, x2, y2, angle): overlap / max(sa + sb - overlap,
+ * 1e-8), out[na, nb]. */
+int msmd_boxes_iou_bev_f32(const float* boxes_a /* [na,5] */, int na,
+                           const float* boxes_b /* [nb,5] */, int nb,
+                           float* out /* [na,nb] */, msmd_stream_t stream);
+/* Greedy NMS of num_segments lists in one call, nothing read back.  Segment s is rows
+ * offsets[s] .. offsets[s+1] of boxes (row stride ld floats), already in descending score
+ * order; only its first max_segment rows take part (the pre-NMS cut; max_segment <= 16384,
+ * else MSMD_ERR_INVALID_ARG before anything is enqueued).  Row i suppresses a later row j when
+ *   kind 0 (rotated): iou_bev(i, j) > thresh[s]      columns x1, y1, x2, y2, angle
+ *   kind 1 (normal):  iou_normal(i, j) > thresh[s]   columns x1, y1, x2, y2
+ *   kind 2 (circle):  dx*dx + dy*dy <= thresh[s]     columns x, y; float32, no contraction
+ * NaN follows these expressions as written.  Kinds 0 and 2: every test is false, the box is
+ * kept and suppresses nothing.  Kind 1: iou_normal's fmaxf / fminf drop the NaN and its union
+ * becomes fmaxf(NaN, 1e-8) = 1e-8, so a NaN box counts as overlapping, as in the reference.
+ * keep[s * keep_stride + p] = the p-th kept row of segment s for p < num_keep[s] =
+ * min(kept, post_max, keep_stride), -1 after that: the row's position in the segment, or
+ * order[offsets[s] + position] when order is given (the caller's sort permutation).
+ * workspace: the suppression mask, total_boxes * ceil(max_segment / 64) words.
+ * Bitwise reproducible: no atomics on floats, launch sizes depend on the arguments only. */
+size_t msmd_nms_workspace_bytes(int total_boxes, int max_segment);
+int msmd_nms_batched_f32(int kind, const float* boxes /* [total_boxes, ld] */, int ld,
+                         const int32_t* offsets /* [num_segments + 1] */, int num_segments,
+                         int total_boxes, int max_segment,
+                         const float* thresh /* [num_segments] */, int post_max,
+                         const int64_t* order /* [total_boxes] or NULL */,
+                         int64_t* keep /* [num_segments, keep_stride] */, int keep_stride,
+                         int32_t* num_keep /* [num_segments] */, void* workspace,
+                         size_t workspace_bytes, msmd_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * p1  Pillar feature net: decoration + Linear + BatchNorm1d + ReLU + max / mean over the slots
  * replaces: PillarFeatureNet.forward  mmdet3d/models/voxel_encoders/pillar_encoder.py:91-150
  *           PFNLayer.forward          mmdet3d/models/voxel_encoders/utils.py:191-227

@@ -155,6 +155,98 @@ TRANSFUSION_PILLAR_L = dict(
     freeze_lidar_components=False)
 
 
+# ---------------------------------------------------------------------------------------------
+# CenterPoint (configs/_base_/models/centerpoint_{01voxel,02pillar}_second_secfpn_nus.py under
+# configs/centerpoint/*): the `model` dicts after the `_base_` merge.  VOXEL: the 0.075 m
+# voxel chain with circle NMS (centerpoint_0075voxel_second_secfpn_circlenms_4x8_cyclic_20e_nus
+# .py); PILLAR: centerpoint_02pillar_second_secfpn_4x8_cyclic_20e_nus.py (rotated NMS).
+# tests/golden/reference_centerpoint_configs.json holds the reference's values.
+# NOTE: this fork's CenterHead.get_targets_single reads train_cfg['pc_range'], which these
+# stock dicts do not carry (they carry point_cloud_range): add it before training, as the
+# fork's own MSMD_centerpoint_* configs do.
+_CENTERPOINT_TASKS = [
+    dict(num_class=1, class_names=["car"]),
+    dict(num_class=2, class_names=["truck", "construction_vehicle"]),
+    dict(num_class=2, class_names=["bus", "trailer"]),
+    dict(num_class=1, class_names=["barrier"]),
+    dict(num_class=2, class_names=["motorcycle", "bicycle"]),
+    dict(num_class=2, class_names=["pedestrian", "traffic_cone"])]
+_CENTERPOINT_BN = dict(type="BN", eps=0.001, momentum=0.01)
+
+
+def _centerpoint_head(in_channels, out_size_factor, voxel_size, pc_range):
+    return dict(
+        type="CenterHead", in_channels=in_channels, tasks=_CENTERPOINT_TASKS,
+        common_heads=dict(reg=(2, 2), height=(1, 2), dim=(3, 2), rot=(2, 2), vel=(2, 2)),
+        share_conv_channel=64,
+        bbox_coder=dict(type="CenterPointBBoxCoder",
+                        post_center_range=[-61.2, -61.2, -10.0, 61.2, 61.2, 10.0], max_num=500,
+                        score_threshold=0.1, out_size_factor=out_size_factor,
+                        voxel_size=voxel_size[:2], pc_range=pc_range[:2], code_size=9),
+        separate_head=dict(type="SeparateHead", init_bias=-2.19, final_kernel=3),
+        loss_cls=dict(type="GaussianFocalLoss", reduction="mean"),
+        loss_bbox=dict(type="L1Loss", reduction="mean", loss_weight=0.25), norm_bbox=True)
+
+
+def _centerpoint_cfgs(grid_size, out_size_factor, voxel_size, pc_range, nms_type):
+    train = dict(pts=dict(grid_size=grid_size, voxel_size=voxel_size,
+                          out_size_factor=out_size_factor, dense_reg=1, gaussian_overlap=0.1,
+                          max_objs=500, min_radius=2,
+                          code_weights=[1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 0.2, 0.2],
+                          point_cloud_range=pc_range))
+    test = dict(pts=dict(post_center_limit_range=[-61.2, -61.2, -10.0, 61.2, 61.2, 10.0],
+                         max_per_img=500, max_pool_nms=False,
+                         min_radius=[4, 12, 10, 1, 0.85, 0.175], score_threshold=0.1,
+                         out_size_factor=out_size_factor, voxel_size=voxel_size[:2],
+                         pc_range=pc_range[:2], nms_type=nms_type, pre_max_size=1000,
+                         post_max_size=83, nms_thr=0.2))
+    return train, test
+
+
+_CP_VOXEL_SIZE, _CP_VOXEL_RANGE = [0.075, 0.075, 0.2], [-54, -54, -5.0, 54, 54, 3.0]
+_CP_VOXEL_TRAIN, _CP_VOXEL_TEST = _centerpoint_cfgs([1440, 1440, 40], 8, _CP_VOXEL_SIZE,
+                                                    _CP_VOXEL_RANGE, "circle")
+CENTERPOINT_VOXEL_NUS = dict(model=dict(
+    type="CenterPoint",
+    pts_voxel_layer=dict(max_num_points=10, voxel_size=_CP_VOXEL_SIZE, max_voxels=(90000, 120000),
+                         point_cloud_range=_CP_VOXEL_RANGE),
+    pts_voxel_encoder=dict(type="HardSimpleVFE", num_features=5),
+    pts_middle_encoder=dict(
+        type="SparseEncoder", in_channels=5, sparse_shape=[41, 1440, 1440], output_channels=128,
+        order=("conv", "norm", "act"),
+        encoder_channels=((16, 16, 32), (32, 32, 64), (64, 64, 128), (128, 128)),
+        encoder_paddings=((0, 0, 1), (0, 0, 1), (0, 0, [0, 1, 1]), (0, 0)),
+        block_type="basicblock"),
+    pts_backbone=dict(type="SECOND", in_channels=256, out_channels=[128, 256], layer_nums=[5, 5],
+                      layer_strides=[1, 2], norm_cfg=_CENTERPOINT_BN,
+                      conv_cfg=dict(type="Conv2d", bias=False)),
+    pts_neck=dict(type="SECONDFPN", in_channels=[128, 256], out_channels=[256, 256],
+                  upsample_strides=[1, 2], norm_cfg=_CENTERPOINT_BN,
+                  upsample_cfg=dict(type="deconv", bias=False), use_conv_for_no_stride=True),
+    pts_bbox_head=_centerpoint_head(512, 8, _CP_VOXEL_SIZE, _CP_VOXEL_RANGE),
+    train_cfg=_CP_VOXEL_TRAIN, test_cfg=_CP_VOXEL_TEST))
+
+_CP_PILLAR_TRAIN, _CP_PILLAR_TEST = _centerpoint_cfgs([512, 512, 1], 4, PILLAR_VOXEL_SIZE,
+                                                      PILLAR_POINT_CLOUD_RANGE, "rotate")
+CENTERPOINT_PILLAR_NUS = dict(model=dict(
+    type="CenterPoint",
+    pts_voxel_layer=dict(max_num_points=20, voxel_size=PILLAR_VOXEL_SIZE,
+                         max_voxels=(30000, 40000), point_cloud_range=PILLAR_POINT_CLOUD_RANGE),
+    pts_voxel_encoder=dict(type="PillarFeatureNet", in_channels=5, feat_channels=[64],
+                           with_distance=False, voxel_size=(0.2, 0.2, 8),
+                           norm_cfg=dict(type="BN1d", eps=0.001, momentum=0.01), legacy=False,
+                           point_cloud_range=PILLAR_POINT_CLOUD_RANGE),
+    pts_middle_encoder=dict(type="PointPillarsScatter", in_channels=64, output_shape=(512, 512)),
+    pts_backbone=dict(type="SECOND", in_channels=64, out_channels=[64, 128, 256],
+                      layer_nums=[3, 5, 5], layer_strides=[2, 2, 2], norm_cfg=_CENTERPOINT_BN,
+                      conv_cfg=dict(type="Conv2d", bias=False)),
+    pts_neck=dict(type="SECONDFPN", in_channels=[64, 128, 256], out_channels=[128, 128, 128],
+                  upsample_strides=[0.5, 1, 2], norm_cfg=_CENTERPOINT_BN,
+                  upsample_cfg=dict(type="deconv", bias=False), use_conv_for_no_stride=True),
+    pts_bbox_head=_centerpoint_head(384, 4, PILLAR_VOXEL_SIZE, PILLAR_POINT_CLOUD_RANGE),
+    train_cfg=_CP_PILLAR_TRAIN, test_cfg=_CP_PILLAR_TEST))
+
+
 def build_hot_path(cfg):
     """(Voxelization, voxel encoder, SparseEncoder, multimodal encoder | None) from one of
     the dicts above -- what MSMDFusionDetector.__init__ / MVXTwoStageDetector.__init__ build

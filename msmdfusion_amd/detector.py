@@ -52,9 +52,13 @@ def _build_head(cfg, train_cfg, test_cfg, rows):
     if isinstance(cfg, nn.Module):
         return cfg
     args = {k: v for k, v in cfg.items() if k != "type"}
-    if cfg.get("type", "TransFusionHead") != "TransFusionHead":
-        raise KeyError("pts_bbox_head type %r is not built here" % cfg.get("type"))
     pts = lambda c: (c or {}).get("pts", c) if isinstance(c, dict) else c
+    kind = cfg.get("type", "TransFusionHead")
+    if kind == "CenterHead":
+        from .registry import build_head
+        return build_head(dict(cfg, train_cfg=pts(train_cfg), test_cfg=pts(test_cfg)))
+    if kind != "TransFusionHead":
+        raise KeyError("pts_bbox_head type %r is not built here" % kind)
     return TransFusionHead(train_cfg=pts(train_cfg), test_cfg=pts(test_cfg), rows=rows, **args)
 
 
@@ -254,6 +258,25 @@ class TransFusionDetector(nn.Module):
         if return_loss:
             return self.forward_train(points=points, prepared=prepared, **kw)
         return self.extract_pts_feat(points, *extra, prepared=prepared, **kw)
+
+
+@DETECTORS.register_module()
+class CenterPoint(TransFusionDetector):
+    """mmdet3d/models/detectors/centerpoint.py: the same voxelize -> encoder -> SECOND ->
+    SECONDFPN path with CenterHead on the neck's maps (configs.CENTERPOINT_VOXEL_NUS /
+    CENTERPOINT_PILLAR_NUS)."""
+
+    def forward_pts_train(self, pts_feats, img_feats, gt_bboxes_3d, gt_labels_3d, img_metas=None):
+        """centerpoint.py:52-76."""
+        outs = self.pts_bbox_head(pts_feats)
+        return self.pts_bbox_head.loss(gt_bboxes_3d, gt_labels_3d, outs)
+
+    def simple_test(self, points, img_metas=None, img=None, **kw):
+        """centerpoint.py:78-87 (simple_test_pts + bbox3d2result's fields)."""
+        _, pts_feats = self.extract_feat(points, img=img, img_metas=img_metas, **kw)
+        outs = self.pts_bbox_head(pts_feats)
+        return [dict(boxes_3d=b, scores_3d=s, labels_3d=l)
+                for b, s, l in self.pts_bbox_head.get_bboxes(outs, img_metas)]
 
 
 _WARNED = {}

@@ -7,7 +7,8 @@ torch.nn.MultiheadAttention's parameters and arithmetic), FFN (:507-591), TransF
 Built here: the path the LC config takes (`fuse_img` unset, `initialize_by_heatmap=True`,
 one decoder layer, configs/MSMDFusion_nusc_voxel_LC.py:207-241) -- forward_single's
 heatmap-initialised queries, the decoder layers over the flattened BEV map, the prediction
-heads, and get_bboxes' score composition + box decoding without NMS (`nms_type=None`).
+heads, and get_bboxes' score composition + box decoding, with the per-class-group circle /
+rotated NMS of `nms_type` through iou3d.nms_batched.
 The training half -- get_targets (HungarianAssigner3D, heat-map targets) and loss
 (:1051-1286) -- lives in msmdfusion_amd/head_loss.py and is reached through this class's
 `get_targets` / `loss`.  Not built: the image-fusion decoder stages (`fuse_img=True`), the
@@ -26,6 +27,8 @@ import os
 import torch
 from torch import nn
 from torch.nn import functional as F
+
+from .registry import HEADS
 
 
 class Conv1d(nn.Conv1d):
@@ -186,6 +189,7 @@ class TransFusionBBoxCoder:
                 for i in range(heatmap.shape[0])]
 
 
+@HEADS.register_module()
 class TransFusionHead(nn.Module):
     """The LiDAR branch of transfusion_head.py:594-1379 (see the module docstring)."""
 
@@ -374,20 +378,78 @@ class TransFusionHead(nn.Module):
         from . import head_loss as HL
         return HL.loss(self, gt_bboxes_3d, gt_labels_3d, preds_dicts)
 
+    # transfusion_head.py:1316-1328: the class groups NMS runs in, by test_cfg['dataset']
+    NMS_TASKS = {
+        "nuScenes": [dict(num_class=8, class_names=[], indices=[0, 1, 2, 3, 4, 5, 6, 7], radius=-1),
+                     dict(num_class=1, class_names=["pedestrian"], indices=[8], radius=0.175),
+                     dict(num_class=1, class_names=["traffic_cone"], indices=[9], radius=0.175)],
+        "Waymo": [dict(num_class=1, class_names=["Car"], indices=[0], radius=0.7),
+                  dict(num_class=1, class_names=["Pedestrian"], indices=[1], radius=0.7),
+                  dict(num_class=1, class_names=["Cyclist"], indices=[2], radius=0.7)],
+    }
+
     def get_bboxes(self, preds_dicts):
-        """:1285-1379 with nms_type None: score = sigmoid(heatmap) * query heatmap score *
-        one-hot(query class) over the LAST layer's proposals, boxes decoded and filtered by
-        post_center_range / score_threshold.  -> per sample dict(bboxes [n, code], scores,
-        labels); the reference additionally wraps bboxes in its box class."""
-        if self.test_cfg.get("nms_type") is not None:
-            raise NotImplementedError("circle / rotated NMS after decoding is not built "
-                                      "(the LC config runs with nms_type=None)")
+        """:1285-1379: score = sigmoid(heatmap) * query heatmap score * one-hot(query class)
+        over the LAST layer's proposals, boxes decoded and filtered by post_center_range /
+        score_threshold; with test_cfg['nms_type'] 'circle' or 'rotate', NMS inside each class
+        group of NMS_TASKS (a group with radius <= 0 keeps everything, a class in no group is
+        dropped), all groups of all samples in one device call.  -> per sample dict(bboxes
+        [n, code], scores, labels) in decode order; the reference additionally wraps bboxes in
+        its box class."""
         (pred,) = preds_dicts[0] if isinstance(preds_dicts[0], (list, tuple)) else (preds_dicts[0],)
         n = self.num_proposals
         score = pred["heatmap"][..., -n:].sigmoid()
         one_hot = F.one_hot(self.query_labels, num_classes=self.num_classes).permute(0, 2, 1)
         score = score * pred["query_heatmap_score"] * one_hot
         vel = pred["vel"][..., -n:] if "vel" in pred else None
-        return self.bbox_coder.decode(score, pred["rot"][..., -n:], pred["dim"][..., -n:],
+        rets = self.bbox_coder.decode(score, pred["rot"][..., -n:], pred["dim"][..., -n:],
                                       pred["center"][..., -n:], pred["height"][..., -n:], vel,
                                       filter=True)
+        nms_type = self.test_cfg.get("nms_type")
+        if nms_type is None:
+            return rets
+        if nms_type not in ("circle", "rotate"):
+            raise ValueError("nms_type must be None, 'circle' or 'rotate', got %r" % (nms_type,))
+        return self._nms(rets, nms_type, self.NMS_TASKS[self.test_cfg["dataset"]])
+
+    def _nms(self, rets, nms_type, tasks):
+        from . import iou3d
+        boxes = torch.cat([r["bboxes"] for r in rets])
+        scores = torch.cat([r["scores"] for r in rets])
+        sizes = [int(r["scores"].shape[0]) for r in rets]
+        keep_mask = torch.zeros(boxes.shape[0], dtype=torch.bool, device=boxes.device)
+        rows, counts, thresh, base = [], [], [], 0
+        for r, size in zip(rets, sizes):
+            for task in tasks:
+                member = torch.zeros_like(r["labels"], dtype=torch.bool)
+                for cls_idx in task["indices"]:
+                    member |= r["labels"] == cls_idx
+                idx = torch.where(member)[0] + base
+                if task["radius"] > 0:
+                    rows.append(idx)
+                    counts.append(int(idx.numel()))
+                    thresh.append(float(task["radius"]))
+                else:
+                    keep_mask[idx] = True
+            base += size
+        if rows:
+            rows = torch.cat(rows)
+            offsets = torch.tensor([0] + counts, dtype=torch.int32).cumsum(0).to(
+                boxes.device, dtype=torch.int32)
+            longest = max(counts)          # (already on the host) bounds the mask and the grid
+            if nms_type == "circle":       # circle_nms's default post_max_size (box3d_nms.py:142)
+                keep, _ = iou3d.nms_batched("circle", boxes[rows][:, :2].contiguous(),
+                                            scores[rows], offsets, thresh, longest, 83)
+            else:
+                bev = iou3d.xywhr2xyxyr(boxes[rows][:, [0, 1, 3, 4, 6]])
+                pre = self.test_cfg["pre_maxsize"]
+                keep, _ = iou3d.nms_batched("rotate", bev, scores[rows], offsets, thresh,
+                                            longest if pre is None else min(pre, longest),
+                                            self.test_cfg["post_maxsize"])
+            keep_mask[rows[keep[keep >= 0]]] = True
+        out, base = [], 0
+        for r, size in zip(rets, sizes):
+            m = keep_mask[base:base + size]
+            out.append(dict(bboxes=r["bboxes"][m], scores=r["scores"][m], labels=r["labels"][m]))
+            base += size
+        return out

@@ -17,4 +17,4 @@ TV_ASSERT_RT_ERR / TORCH_CHECK.  tests/test_gpu_integration.py calls each of the
 the way the reference's Python does and checks the results against the oracle.
 """
 from . import (furthest_point_sample_ext, gather_points_ext, group_points_ext,  # noqa: F401
-               interpolate_ext, knn_ext, roiaware_pool3d_ext, sparse_conv_ext, voxel_layer)
+               interpolate_ext, iou3d_cuda, knn_ext, roiaware_pool3d_ext, sparse_conv_ext, voxel_layer)

@@ -1784,6 +1784,74 @@ def gaussian_focal(logits, target, clip=1e-4, want_grad=True):
     return sums, grad
 
 
+# ------------------------------------------------ iou3d: BEV IoU and NMS (row n2)
+def boxes_iou_bev(boxes_a, boxes_b):
+    """iou3d_cuda.boxes_iou_bev_gpu: rotated rectangles (x1, y1, x2, y2, angle) -> IoU [na, nb]."""
+    _need_cuda(boxes_a, boxes_b)
+    a, b = boxes_a.contiguous().float(), boxes_b.contiguous().float()
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != 5 or b.shape[1] != 5:
+        raise ValueError("boxes must be [n,5] (x1, y1, x2, y2, angle)")
+    out = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float32, device=a.device)
+    check(lib.msmd_boxes_iou_bev_f32(_p(a), a.shape[0], _p(b), b.shape[0], _p(out), _stream()),
+          "msmd_boxes_iou_bev_f32")
+    return out
+
+
+NMS_KINDS = {"rotate": 0, "rotated": 0, "normal": 1, "circle": 2}
+NMS_MAX_SEGMENT = 16384
+
+
+def nms_workspace_bytes(total_boxes, max_segment):
+    return lib.msmd_nms_workspace_bytes(int(total_boxes), int(max_segment))
+
+
+def nms_segments(kind, boxes, offsets, thresh, max_segment, post_max=None, order=None,
+                 keep=None, num_keep=None, workspace=None):
+    """Greedy NMS of every segment in one call (two launches, nothing read back).
+    boxes [total, >= 5 | 4 | 2] float32, each segment (rows offsets[s] .. offsets[s+1], int32
+    [S + 1] on the device) already in descending score order; only the first `max_segment`
+    rows of a segment take part.  thresh: float32 [S] on the device.  order (optional, long
+    [total]): the caller's sort permutation -- kept rows are then reported as order[row].
+    -> (keep long [S, min(post_max, max_segment)], -1 past num_keep[s]; num_keep int32 [S]).
+    keep / num_keep / workspace (uint8, nms_workspace_bytes) may be passed in: with all three
+    the call allocates nothing."""
+    _need_cuda(boxes, offsets, thresh, order, keep, num_keep, workspace)
+    code = NMS_KINDS[kind]
+    if boxes.dtype != torch.float32 or boxes.dim() != 2 or not boxes.is_contiguous():
+        raise ValueError("boxes must be a contiguous float32 [total, columns] tensor")
+    if offsets.dtype != torch.int32 or thresh.dtype != torch.float32:
+        raise ValueError("offsets must be int32 and thresh float32")
+    segments = offsets.numel() - 1
+    if segments < 0 or thresh.numel() != segments:
+        raise ValueError("offsets holds S + 1 entries and thresh S")
+    total, max_segment = boxes.shape[0], int(max_segment)
+    if max_segment > NMS_MAX_SEGMENT:
+        raise ValueError("NMS handles at most %d boxes per segment (got %d): set pre_max"
+                         % (NMS_MAX_SEGMENT, max_segment))
+    stride = max_segment if post_max is None else min(int(post_max), max_segment)
+    post = stride
+    if order is not None and (order.dtype != torch.long or order.numel() != total):
+        raise ValueError("order must be a long tensor with one entry per box")
+    if keep is None:
+        keep = torch.empty((segments, stride), dtype=torch.long, device=boxes.device)
+    elif keep.dtype != torch.long or tuple(keep.shape) != (segments, stride) \
+            or not keep.is_contiguous():
+        raise ValueError("keep must be a contiguous long [%d, %d] tensor" % (segments, stride))
+    if num_keep is None:
+        num_keep = torch.empty((segments,), dtype=torch.int32, device=boxes.device)
+    elif num_keep.dtype != torch.int32 or num_keep.numel() != segments:
+        raise ValueError("num_keep must be an int32 [%d] tensor" % segments)
+    nbytes = lib.msmd_nms_workspace_bytes(total, max_segment)
+    ws = _ws(nbytes, boxes.device) if workspace is None else workspace
+    if ws.numel() * ws.element_size() < nbytes:
+        raise ValueError("workspace holds %d bytes, %d needed" % (ws.numel(), nbytes))
+    check(lib.msmd_nms_batched_f32(code, _p(boxes), boxes.shape[1], _p(offsets.contiguous()),
+                                   segments, total, max_segment, _p(thresh.contiguous()), post,
+                                   _p(order), _p(keep), stride, _p(num_keep), _p(ws), nbytes,
+                                   _stream()), "msmd_nms_batched_f32")
+    return keep, num_keep
+
+
 def sparse_add(feat_a, idx_a, feat_b, idx_b, batch_size, spatial_shape):
     """-> (out_indices, out_feat, map_a, map_b)"""
     _need_bzyx(idx_a, idx_b)

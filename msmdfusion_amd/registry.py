@@ -57,6 +57,7 @@ BACKBONES = Registry("backbone")
 NECKS = Registry("neck")
 DETECTORS = Registry("detector")
 ROI_EXTRACTORS = Registry("roi_extractor")
+HEADS = Registry("head")
 
 CONV_LAYERS.register_module("Conv1d", module=nn.Conv1d)
 CONV_LAYERS.register_module("Conv2d", module=nn.Conv2d)
@@ -130,3 +131,10 @@ def build_roi_extractor(cfg):
     """mmdet.models.builder.build_roi_extractor (Part-A2's Single3DRoIAwareExtractor)."""
     from . import roiaware_pool3d  # noqa: F401
     return ROI_EXTRACTORS.build(cfg)
+
+
+def build_head(cfg, **kwargs):
+    """mmdet3d.models.builder.build_head: CenterHead / SeparateHead (center_head.py) and
+    TransFusionHead (head.py)."""
+    from . import center_head, head  # noqa: F401
+    return HEADS.build(cfg, **kwargs)
