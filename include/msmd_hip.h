@@ -1247,6 +1247,92 @@ int msmd_point_scatter_bwd_f32(const float* grad_out, const float* weight /* [b,
                                int n, int m, int dest_per_out, int accumulate,
                                float* grad_in /* [b,c,n] */, msmd_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * n3  Anchor3DHead: matrix-free target assignment and the sigmoid focal loss (csrc/anchor.hip)
+ * replaces: MaxIoUAssigner.assign / assign_wrt_overlaps (mmdet 2.x
+ *           mmdet/core/bbox/assigners/max_iou_assigner.py) over BboxOverlapsNearest3D
+ *           (mmdet3d/core/bbox/iou_calculators/iou3d_calculator.py:94-150 -> mmdet
+ *           bbox_overlaps): a [num_gt, num_anchors] matrix per sample and per assigner,
+ *           reduced along both axes, then a Python loop over the ground truths
+ *           AnchorTrainMixin.anchor_target_3d_single / anchor_target_single_assigner
+ *           (mmdet3d/models/dense_heads/train_mixins.py:101-314), get_direction_target
+ *           (:317-346), DeltaXYZWLHRBBoxCoder.encode
+ *           (mmdet3d/core/bbox/coders/delta_xyzwhlr_bbox_coder.py:20-54)
+ *           mmdet FocalLoss(use_sigmoid=True) as Anchor3DHead.loss_single calls it
+ *           (mmdet3d/models/dense_heads/anchor3d_head.py:217-218)
+ * A segment is one (sample, assigner group): output rows anchor_offsets[s] ..
+ * anchor_offsets[s+1] (a HOST array, ascending from 0: the anchors' layout follows from the
+ * feature-map sizes) and the ground truths gt_index[gt_offsets[s] .. gt_offsets[s+1]) (DEVICE
+ * arrays: under assign_per_class they depend on the labels; gt_index NULL: the entries are the
+ * rows themselves).  Output row r uses anchor row r % anchor_rows, so the samples of a batch
+ * share one copy of the anchors.  At most msmd_anchor_max_segments() segments per call
+ * (MSMD_ERR_RANGE beyond).  Nothing is read back; bad arguments, offsets that do not ascend
+ * included, are refused before anything is enqueued.
+ * ------------------------------------------------------------------------ */
+int msmd_anchor_max_segments(void);
+/* ground-truth boxes staged in LDS at a time (a test crosses it on purpose) */
+int msmd_anchor_gt_chunk(void);
+/* mmdet 2.x MaxIoUAssigner with match_low_quality, gt_max_assign_all, ignore_iof_thr < 0 and a
+ * scalar neg_iou_thr, on axis-aligned BEV boxes (x1, y1, x2, y2):
+ *   iou = overlap / max(area_gt + area_anchor - overlap, 1e-6), wh = clamp(rb - lt, 0), float32
+ *   1. every anchor starts at -1 (ignored)
+ *   2. 0 <= max < neg_iou_thr[s]: 0 (negative)
+ *   3. max >= pos_iou_thr[s]: argmax + 1, ties to the LOWEST ground-truth index
+ *   4. for ground truths i in ascending order whose best IoU over the segment's anchors is
+ *      >= min_pos_iou[s]: every anchor whose IoU with i EQUALS that best value gets i + 1 (a
+ *      later i overrides an earlier one and rule 3)
+ * with i local to the segment's list.  A segment without ground truths: every anchor 0,
+ * max_overlaps 0.  num_pos[s] = anchors of segment s with assigned_gt > 0.  An entry of
+ * gt_index outside [0, num_gt) is never assigned.  Bitwise reproducible: the only atomics are
+ * integer ones (a max on the bits of the non-negative IoU, a count). */
+size_t msmd_anchor_assign_workspace_bytes(int gt_entries);
+int msmd_anchor_assign_f32(const float* anchor_bev /* [anchor_rows,4] */, int anchor_rows,
+                           const int32_t* anchor_offsets /* HOST [num_segments+1] */,
+                           int num_segments, const float* gt_bev /* [num_gt,4] */, int num_gt,
+                           const int32_t* gt_index /* [gt_entries] or NULL */,
+                           const int32_t* gt_offsets /* [num_segments+1] */, int gt_entries,
+                           const float* pos_iou_thr /* HOST [num_segments] */,
+                           const float* neg_iou_thr /* HOST [num_segments] */,
+                           const float* min_pos_iou /* HOST [num_segments] */,
+                           int32_t* assigned_gt /* [rows] */, float* max_overlaps /* [rows] */,
+                           int32_t* num_pos /* [num_segments] */, void* workspace,
+                           size_t workspace_bytes, msmd_stream_t stream);
+/* From assigned_gt, for input row r of sample r / anchor_rows, written at row
+ * dest[r % anchor_rows] of that sample (dest NULL: in place; a permutation of [0, anchor_rows),
+ * the reference's [..., size, rotation] interleaving when the segments are the anchor sizes):
+ *   positive: bbox_targets = DeltaXYZWLHRBBoxCoder.encode(anchor, gt) (columns past 7:
+ *     gt - anchor), bbox_weights = 1, dir_targets = floor(limit_period(rot_gt - dir_offset, 0,
+ *     2 pi) / pi) clamped to {0, 1} with rot_gt = (gt_r - anchor_r) + anchor_r, dir_weights = 1,
+ *     labels = gt_labels[gt], label_weights = pos_weight > 0 ? pos_weight : 1
+ *   otherwise: labels = num_classes, zeros; label_weights = 1 for a negative, 0 for an ignored
+ *     anchor.
+ * 7 <= code_size <= 16 (else MSMD_ERR_UNSUPPORTED). */
+int msmd_anchor_targets_f32(const int32_t* assigned_gt /* [rows] */,
+                            const float* anchors /* [anchor_rows,code_size] */, int anchor_rows,
+                            int code_size,
+                            const int32_t* anchor_offsets /* HOST [num_segments+1] */,
+                            int num_segments, const float* gt_boxes /* [num_gt,code_size] */,
+                            const int64_t* gt_labels /* [num_gt] */, int num_gt,
+                            const int32_t* gt_index /* [gt_entries] or NULL */,
+                            const int32_t* gt_offsets /* [num_segments+1] */, int gt_entries,
+                            const int32_t* dest /* [anchor_rows] or NULL */, int num_classes,
+                            float pos_weight, float dir_offset, int64_t* labels /* [rows] */,
+                            float* label_weights /* [rows] */,
+                            float* bbox_targets /* [rows,code_size] */,
+                            float* bbox_weights /* [rows,code_size] */,
+                            int64_t* dir_targets /* [rows] */, float* dir_weights /* [rows] */,
+                            msmd_stream_t stream);
+/* sum[0] = sum over i, c of weights[i] * BCE_with_logits(x, t) * (alpha t + (1 - alpha)(1 - t))
+ * * pt^gamma with t = [labels[i] == c] (background: labels[i] == num_classes), pt = (1 - p) t +
+ * p (1 - t), p = sigmoid(x); grad (optional) = d of that sum / d logit.  The avg_factor division
+ * stays with the caller.  Deterministic: per-block partials in double, summed in block order. */
+size_t msmd_sigmoid_focal_workspace_bytes(int64_t n, int num_classes);
+int msmd_sigmoid_focal_f32(const float* logits /* [n,num_classes] */,
+                           const int64_t* labels /* [n] */, const float* weights /* [n] */,
+                           int64_t n, int num_classes, float gamma, float alpha,
+                           float* grad /* [n,num_classes] or NULL */, float* sum /* [1] */,
+                           void* workspace, size_t workspace_bytes, msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -194,6 +194,15 @@ SIGNATURES = {
     "msmd_point_inverse_index_workspace_bytes": (_sz, [_i, _i]),
     "msmd_point_inverse_index": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "msmd_point_scatter_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "msmd_anchor_max_segments": (_i, []),
+    "msmd_anchor_gt_chunk": (_i, []),
+    "msmd_anchor_assign_workspace_bytes": (_sz, [_i]),
+    "msmd_anchor_assign_f32": (_i, [_vp, _i, _ip, _i, _vp, _i, _vp, _vp, _i, _fp, _fp, _fp, _vp, _vp,
+                                    _vp, _vp, _sz, _vp]),
+    "msmd_anchor_targets_f32": (_i, [_vp, _vp, _i, _i, _ip, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _f,
+                                     _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msmd_sigmoid_focal_workspace_bytes": (_sz, [_i64, _i]),
+    "msmd_sigmoid_focal_f32": (_i, [_vp, _vp, _vp, _i64, _i, _f, _f, _vp, _vp, _vp, _sz, _vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -247,6 +247,78 @@ CENTERPOINT_PILLAR_NUS = dict(model=dict(
     train_cfg=_CP_PILLAR_TRAIN, test_cfg=_CP_PILLAR_TEST))
 
 
+# ---------------------------------------------------------------------------------------------
+# PointPillars and SECOND on KITTI (configs/_base_/models/hv_pointpillars_secfpn_kitti.py and
+# hv_second_secfpn_kitti.py, the bases of every configs/pointpillars/*kitti* and
+# configs/second/*kitti* file): VoxelNet with Anchor3DHead, three classes (Pedestrian, Cyclist,
+# Car), one MaxIoUAssigner per anchor size.  tests/golden/reference_anchor_head_configs.json
+# holds the reference's values.
+def _kitti_assigner(pos_iou_thr, neg_iou_thr):
+    return dict(type="MaxIoUAssigner", iou_calculator=dict(type="BboxOverlapsNearest3D"),
+                pos_iou_thr=pos_iou_thr, neg_iou_thr=neg_iou_thr, min_pos_iou=neg_iou_thr,
+                ignore_iof_thr=-1)
+
+
+def _kitti_anchor_head(channels, y_range):
+    return dict(
+        type="Anchor3DHead", num_classes=3, in_channels=channels, feat_channels=channels,
+        use_direction_classifier=True,
+        anchor_generator=dict(
+            type="Anchor3DRangeGenerator",
+            ranges=[[0, -y_range, -0.6, 70.4, y_range, -0.6],
+                    [0, -y_range, -0.6, 70.4, y_range, -0.6],
+                    [0, -y_range, -1.78, 70.4, y_range, -1.78]],
+            sizes=[[0.6, 0.8, 1.73], [0.6, 1.76, 1.73], [1.6, 3.9, 1.56]],
+            rotations=[0, 1.57], reshape_out=False),
+        diff_rad_by_sin=True, bbox_coder=dict(type="DeltaXYZWLHRBBoxCoder"),
+        loss_cls=dict(type="FocalLoss", use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=1.0),
+        loss_bbox=dict(type="SmoothL1Loss", beta=1.0 / 9.0, loss_weight=2.0),
+        loss_dir=dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=0.2))
+
+
+def _kitti_cfgs(small_pos, small_neg):
+    train = dict(assigner=[_kitti_assigner(small_pos, small_neg),      # Pedestrian
+                           _kitti_assigner(small_pos, small_neg),      # Cyclist
+                           _kitti_assigner(0.6, 0.45)],                # Car
+                 allowed_border=0, pos_weight=-1, debug=False)
+    test = dict(use_rotate_nms=True, nms_across_levels=False, nms_thr=0.01, score_thr=0.1,
+                min_bbox_size=0, nms_pre=100, max_num=50)
+    return train, test
+
+
+_KITTI_PILLAR_VOXEL, _KITTI_PILLAR_RANGE = [0.16, 0.16, 4], [0, -39.68, -3, 69.12, 39.68, 1]
+_KITTI_PILLAR_TRAIN, _KITTI_PILLAR_TEST = _kitti_cfgs(0.5, 0.35)
+POINTPILLARS_SECFPN_KITTI = dict(model=dict(
+    type="VoxelNet",
+    voxel_layer=dict(max_num_points=32, point_cloud_range=_KITTI_PILLAR_RANGE,
+                     voxel_size=_KITTI_PILLAR_VOXEL, max_voxels=(16000, 40000)),
+    voxel_encoder=dict(type="PillarFeatureNet", in_channels=4, feat_channels=[64],
+                       with_distance=False, voxel_size=_KITTI_PILLAR_VOXEL,
+                       point_cloud_range=_KITTI_PILLAR_RANGE),
+    middle_encoder=dict(type="PointPillarsScatter", in_channels=64, output_shape=[496, 432]),
+    backbone=dict(type="SECOND", in_channels=64, layer_nums=[3, 5, 5], layer_strides=[2, 2, 2],
+                  out_channels=[64, 128, 256]),
+    neck=dict(type="SECONDFPN", in_channels=[64, 128, 256], upsample_strides=[1, 2, 4],
+              out_channels=[128, 128, 128]),
+    bbox_head=_kitti_anchor_head(384, 39.68),
+    train_cfg=_KITTI_PILLAR_TRAIN, test_cfg=_KITTI_PILLAR_TEST))
+
+_KITTI_SECOND_TRAIN, _KITTI_SECOND_TEST = _kitti_cfgs(0.35, 0.2)
+SECOND_SECFPN_KITTI = dict(model=dict(
+    type="VoxelNet",
+    voxel_layer=dict(max_num_points=5, point_cloud_range=[0, -40, -3, 70.4, 40, 1],
+                     voxel_size=[0.05, 0.05, 0.1], max_voxels=(16000, 40000)),
+    voxel_encoder=dict(type="HardSimpleVFE"),
+    middle_encoder=dict(type="SparseEncoder", in_channels=4, sparse_shape=[41, 1600, 1408],
+                        order=("conv", "norm", "act")),
+    backbone=dict(type="SECOND", in_channels=256, layer_nums=[5, 5], layer_strides=[1, 2],
+                  out_channels=[128, 256]),
+    neck=dict(type="SECONDFPN", in_channels=[128, 256], upsample_strides=[1, 2],
+              out_channels=[256, 256]),
+    bbox_head=_kitti_anchor_head(512, 40.0),
+    train_cfg=_KITTI_SECOND_TRAIN, test_cfg=_KITTI_SECOND_TEST))
+
+
 def build_hot_path(cfg):
     """(Voxelization, voxel encoder, SparseEncoder, multimodal encoder | None) from one of
     the dicts above -- what MSMDFusionDetector.__init__ / MVXTwoStageDetector.__init__ build

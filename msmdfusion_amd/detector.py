@@ -54,7 +54,7 @@ def _build_head(cfg, train_cfg, test_cfg, rows):
     args = {k: v for k, v in cfg.items() if k != "type"}
     pts = lambda c: (c or {}).get("pts", c) if isinstance(c, dict) else c
     kind = cfg.get("type", "TransFusionHead")
-    if kind == "CenterHead":
+    if kind in ("CenterHead", "Anchor3DHead"):
         from .registry import build_head
         return build_head(dict(cfg, train_cfg=pts(train_cfg), test_cfg=pts(test_cfg)))
     if kind != "TransFusionHead":
@@ -277,6 +277,52 @@ class CenterPoint(TransFusionDetector):
         outs = self.pts_bbox_head(pts_feats)
         return [dict(boxes_3d=b, scores_3d=s, labels_3d=l)
                 for b, s, l in self.pts_bbox_head.get_bboxes(outs, img_metas)]
+
+
+@DETECTORS.register_module()
+class VoxelNet(TransFusionDetector):
+    """mmdet3d/models/detectors/voxelnet.py (SingleStage3DDetector): the same voxelize ->
+    encoder -> SECOND -> SECONDFPN path under the reference's attribute names (`voxel_layer`,
+    `voxel_encoder`, `middle_encoder`, `backbone`, `neck`, `bbox_head`, which are also its
+    state-dict prefixes) with Anchor3DHead on the neck's maps (configs.POINTPILLARS_SECFPN_KITTI
+    / SECOND_SECFPN_KITTI).  The path itself is TransFusionDetector's: its `pts_*` names
+    resolve to these attributes."""
+
+    _ALIAS = dict(pts_voxel_layer="voxel_layer", pts_voxel_encoder="voxel_encoder",
+                  pts_middle_encoder="middle_encoder", pts_backbone="backbone", pts_neck="neck",
+                  pts_bbox_head="bbox_head")
+
+    def __init__(self, voxel_layer=None, voxel_encoder=None, middle_encoder=None, backbone=None,
+                 neck=None, bbox_head=None, train_cfg=None, test_cfg=None, pretrained=None,
+                 init_cfg=None, **kwargs):
+        super().__init__(pts_voxel_layer=voxel_layer, pts_voxel_encoder=voxel_encoder,
+                         pts_middle_encoder=middle_encoder, pts_backbone=backbone, pts_neck=neck,
+                         pts_bbox_head=bbox_head, train_cfg=train_cfg, test_cfg=test_cfg,
+                         pretrained=pretrained, **kwargs)
+
+    def __setattr__(self, name, value):
+        # the base constructor assigns the six pts_* names: they land under the reference's
+        super().__setattr__(self._ALIAS.get(name, name), value)
+
+    pts_voxel_layer = property(lambda self: self.voxel_layer)
+    pts_voxel_encoder = property(lambda self: self.voxel_encoder)
+    pts_middle_encoder = property(lambda self: self.middle_encoder)
+    pts_backbone = property(lambda self: self.backbone)
+    pts_neck = property(lambda self: self.neck)
+    pts_bbox_head = property(lambda self: self.bbox_head)
+
+    def forward_pts_train(self, pts_feats, img_feats, gt_bboxes_3d, gt_labels_3d, img_metas=None):
+        """voxelnet.py:67-96."""
+        outs = self.bbox_head(pts_feats)
+        return self.bbox_head.loss(*outs, gt_bboxes_3d, gt_labels_3d, img_metas)
+
+    def simple_test(self, points, img_metas=None, imgs=None, rescale=False, **kw):
+        """voxelnet.py:98-108 (bbox3d2result's fields)."""
+        _, pts_feats = self.extract_feat(points, img_metas=img_metas, **kw)
+        outs = self.bbox_head(pts_feats)
+        metas = img_metas if img_metas is not None else [None] * len(points)
+        return [dict(boxes_3d=b, scores_3d=s, labels_3d=l)
+                for b, s, l in self.bbox_head.get_bboxes(*outs, metas, rescale=rescale)]
 
 
 _WARNED = {}

@@ -1852,6 +1852,123 @@ def nms_segments(kind, boxes, offsets, thresh, max_segment, post_max=None, order
     return keep, num_keep
 
 
+# ------------------------------------------------ Anchor3DHead targets / loss (row n3)
+ANCHOR_MAX_SEGMENTS = lib.msmd_anchor_max_segments()
+ANCHOR_GT_CHUNK = lib.msmd_anchor_gt_chunk()
+
+
+def _host_ints(v):
+    return (C.c_int * len(v))(*[int(x) for x in v])
+
+
+def _gt_lists(gt_index, gt_offsets, segments, num_gt):
+    _need_cuda(gt_index, gt_offsets)
+    if gt_offsets.dtype != torch.int32 or gt_offsets.numel() != segments + 1:
+        raise ValueError("gt_offsets must be an int32 tensor of one entry per segment plus one")
+    if gt_index is None:
+        return None, int(num_gt)
+    if gt_index.dtype != torch.int32:
+        raise ValueError("gt_index must be int32")
+    return gt_index.contiguous(), int(gt_index.numel())
+
+
+def anchor_assign(anchor_bev, anchor_offsets, gt_bev, gt_offsets, pos_iou_thr, neg_iou_thr,
+                  min_pos_iou, gt_index=None):
+    """MaxIoUAssigner over nearest-BEV boxes for every (sample, assigner group) segment in one
+    call, without the IoU matrix and with nothing read back (include/msmd_hip.h, row n3).
+    anchor_bev [rows, 4] float32 (x1, y1, x2, y2), shared by the samples: output row r uses
+    anchor row r % rows.  anchor_offsets: a HOST sequence [S + 1], ascending from 0.  gt_bev
+    [G, 4]; gt_offsets int32 [S + 1] on the device, into gt_index (int32, device) or, without
+    it, into gt_bev itself.  Thresholds: one float per segment (host).
+    -> assigned_gt int32 [total] (-1 ignored, 0 negative, i + 1 positive with i local to the
+       segment's list), max_overlaps float32 [total], num_pos int32 [S]."""
+    _need_cuda(anchor_bev, gt_bev)
+    offs = [int(v) for v in anchor_offsets]
+    segments = len(offs) - 1
+    if segments < 0 or not (len(pos_iou_thr) == len(neg_iou_thr) == len(min_pos_iou) == segments):
+        raise ValueError("anchor_offsets holds S + 1 entries and every threshold list S")
+    a, g = anchor_bev.contiguous(), gt_bev.contiguous()
+    if a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 4 or g.dtype != torch.float32 \
+            or g.dim() != 2 or g.shape[1] != 4:
+        raise ValueError("anchor_bev and gt_bev must be float32 [n, 4] (x1, y1, x2, y2)")
+    gt_index, entries = _gt_lists(gt_index, gt_offsets, segments, g.shape[0])
+    total = offs[-1] if segments >= 0 and offs else 0
+    dev = a.device
+    assigned = torch.empty((max(total, 0),), dtype=torch.int32, device=dev)
+    overlaps = torch.empty((max(total, 0),), dtype=torch.float32, device=dev)
+    num_pos = torch.empty((segments,), dtype=torch.int32, device=dev)
+    nbytes = lib.msmd_anchor_assign_workspace_bytes(entries)
+    ws = _ws(nbytes, dev)
+    check(lib.msmd_anchor_assign_f32(_p(a), a.shape[0], _host_ints(offs), segments, _p(g),
+                                     g.shape[0], _p(gt_index), _p(gt_offsets.contiguous()),
+                                     entries, float_arr(pos_iou_thr), float_arr(neg_iou_thr),
+                                     float_arr(min_pos_iou), _p(assigned), _p(overlaps),
+                                     _p(num_pos), _p(ws), nbytes, _stream()),
+          "msmd_anchor_assign_f32")
+    return assigned, overlaps, num_pos
+
+
+def anchor_targets(assigned_gt, anchors, anchor_offsets, gt_boxes, gt_labels, gt_offsets,
+                   num_classes, pos_weight=-1.0, dir_offset=0.0, gt_index=None, dest=None):
+    """The tensors anchor_target_single_assigner writes, for every segment at once, from
+    anchor_assign's assigned_gt.  anchors [rows, code], gt_boxes [G, code] float32, gt_labels
+    long [G]; dest (int32 [rows], device): where row r of a sample lands in that sample's
+    output (the reference's size-interleaved order).
+    -> labels long [total], label_weights, bbox_targets [total, code], bbox_weights,
+       dir_targets long [total], dir_weights."""
+    _need_cuda(assigned_gt, anchors, gt_boxes, gt_labels, dest)
+    offs = [int(v) for v in anchor_offsets]
+    segments = len(offs) - 1
+    a, g = anchors.contiguous(), gt_boxes.contiguous()
+    if a.dtype != torch.float32 or g.dtype != torch.float32 or a.dim() != 2 or g.dim() != 2 \
+            or a.shape[1] != g.shape[1]:
+        raise ValueError("anchors and gt_boxes must be float32 [n, code] with one code size")
+    if gt_labels.dtype != torch.long or gt_labels.numel() != g.shape[0]:
+        raise ValueError("gt_labels must be a long tensor with one entry per box")
+    total = offs[-1]
+    if assigned_gt.dtype != torch.int32 or assigned_gt.numel() != total:
+        raise ValueError("assigned_gt must be int32 with one entry per output row")
+    if dest is not None and (dest.dtype != torch.int32 or dest.numel() != a.shape[0]):
+        raise ValueError("dest must be int32 with one entry per anchor row")
+    gt_index, entries = _gt_lists(gt_index, gt_offsets, segments, g.shape[0])
+    dev, code = a.device, a.shape[1]
+    labels = torch.empty((total,), dtype=torch.long, device=dev)
+    label_weights = torch.empty((total,), dtype=torch.float32, device=dev)
+    bbox_targets = torch.empty((total, code), dtype=torch.float32, device=dev)
+    bbox_weights = torch.empty((total, code), dtype=torch.float32, device=dev)
+    dir_targets = torch.empty((total,), dtype=torch.long, device=dev)
+    dir_weights = torch.empty((total,), dtype=torch.float32, device=dev)
+    check(lib.msmd_anchor_targets_f32(
+        _p(assigned_gt.contiguous()), _p(a), a.shape[0], code, _host_ints(offs), segments, _p(g),
+        _p(gt_labels.contiguous()), g.shape[0], _p(gt_index), _p(gt_offsets.contiguous()), entries,
+        _p(dest), int(num_classes), float(pos_weight), float(dir_offset), _p(labels),
+        _p(label_weights), _p(bbox_targets), _p(bbox_weights), _p(dir_targets), _p(dir_weights),
+        _stream()), "msmd_anchor_targets_f32")
+    return labels, label_weights, bbox_targets, bbox_weights, dir_targets, dir_weights
+
+
+def sigmoid_focal(logits, labels, weights, gamma=2.0, alpha=0.25, want_grad=True):
+    """mmdet FocalLoss(use_sigmoid=True), weighted and summed: logits [N, C] float32, labels
+    long [N] (background = C), weights float32 [N].
+    -> (sum float32 [1], grad like logits | None)"""
+    _need_cuda(logits, labels, weights)
+    x = logits.contiguous()
+    if x.dtype != torch.float32 or x.dim() != 2:
+        raise ValueError("logits must be float32 [N, C]")
+    n, c = x.shape
+    if labels.dtype != torch.long or labels.numel() != n or weights.dtype != torch.float32 \
+            or weights.numel() != n:
+        raise ValueError("labels (long) and weights (float32) hold one entry per row of logits")
+    total = torch.empty((1,), dtype=torch.float32, device=x.device)
+    grad = torch.empty_like(x) if want_grad else None
+    nbytes = lib.msmd_sigmoid_focal_workspace_bytes(n, c)
+    ws = _ws(nbytes, x.device)
+    check(lib.msmd_sigmoid_focal_f32(_p(x), _p(labels.contiguous()), _p(weights.contiguous()), n, c,
+                                     float(gamma), float(alpha), _p(grad), _p(total), _p(ws),
+                                     nbytes, _stream()), "msmd_sigmoid_focal_f32")
+    return total, grad
+
+
 def sparse_add(feat_a, idx_a, feat_b, idx_b, batch_size, spatial_shape):
     """-> (out_indices, out_feat, map_a, map_b)"""
     _need_bzyx(idx_a, idx_b)
