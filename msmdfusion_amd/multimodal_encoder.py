@@ -355,20 +355,14 @@ class SparseMultiModalEncoderPaint(nn.Module):
                                   geoms)
         out = None
         for i, (lv, cs) in enumerate(zip(levels, downs)):
-            c = cs[0]
             if i == 0:
                 total = plans[0]["unified"]
             else:
                 total = self._shell(lv["total_indices"], shapes[i], batch_size)
                 plans[i]["add"] = Fsp.add_plan(total, lv["map_a"], lv["map_b"])
-            idx = total.indices
-            assert idx is lv["total_indices"] or i == 0
-            ident = (idx.data_ptr(), idx.shape[0], tuple(shapes[i]), tuple(c.kernel_size),
-                     tuple(c.stride), tuple(c.padding), tuple(c.dilation), False)
-            total._rb_cache[ident] = spconv.IndiceData(
-                lv["out_indices"], idx, lv["nbr_fwd"], lv["nbr_bwd"], False, list(shapes[i]),
-                list(lv["out_shape"]), list(c.kernel_size), list(c.stride), list(c.padding),
-                list(c.dilation), None)
+            assert total.indices is lv["total_indices"] or i == 0
+            total.seed_rulebook(cs[0], lv["out_indices"], lv["nbr_fwd"], lv["nbr_bwd"],
+                                lv["out_shape"])
             with spconv.plan_batch("stage"):
                 out = total.plan(spconv.sparse_convs(getattr(self.downscale_blocks,
                                                              f"stage_{i + 1}")), need_grad)

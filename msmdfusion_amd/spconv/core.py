@@ -15,9 +15,11 @@ import numpy as np
 import torch
 
 from .. import kernels as K
+from .functional import ConvNeeds, conv_needs, dense as _dense
 
 
 _PLAN = threading.local()
+_UNSET = object()       # "not computed yet" (None is a result: an empty table has no order)
 # MSMD_PLAN_BATCH=0: every table planned at once by its own prepare() (A/B, tests)
 PLAN_BATCHING = os.environ.get("MSMD_PLAN_BATCH", "1") != "0"
 # MSMD_SUBM_BATCH=0: SubM tables built at once even inside a plan_batch (plans stay batched)
@@ -98,26 +100,22 @@ class plan_batch:
         jobs, todo = list(self.jobs.values()), []
         self.jobs = {}
         for j in jobs:
-            rb, fwd = j["rb"], j["side"] == "fwd"
-            have = rb._prefix_fwd if fwd else rb._prefix_bwd
-            tiled = rb._tiled_fwd if fwd else rb._tiled_bwd
-            order = rb._order_fwd if fwd else rb._order_bwd
-            rows = {r for r in j["tile_rows"] if r not in have}
-            want_table = bool(j["tile_rows"]) and tiled is None
-            if rows and tiled is not None:          # a further height of a table already tiled
+            rb, fwd, side = j["rb"], j["side"] == "fwd", getattr(j["rb"], j["side"])
+            rows = {r for r in j["tile_rows"] if r not in side._prefix}
+            want_table = bool(j["tile_rows"]) and side._tiled is _UNSET
+            if rows and not want_table:             # a further height of a table already tiled
                 for r in rows:
-                    have[r] = K.tile_prefix(tiled[0], r)
+                    side.prefix(r)
                 rows = set()
             want_pairs = fwd and j["want_pairs"] and rb._pairs is None
             want_seg = fwd and j["want_segments"] and rb._pair_segments is False
             if want_seg and rb._pairs is not None:
                 rb.pair_segments()
                 want_seg = False
-            want_order = j["want_order"] and order is None
+            want_order = j["want_order"] and side._order is _UNSET
             if not (rows or want_table or want_pairs or want_seg or want_order):
                 continue
-            todo.append((rb, j["side"], dict(nbr=rb.nbr_fwd if fwd else rb.nbr_bwd, tile_rows=rows,
-                                             want_order=want_order,
+            todo.append((rb, j["side"], dict(nbr=side.nbr, tile_rows=rows, want_order=want_order,
                                              want_table=want_table, want_pairs=want_pairs,
                                              want_segments=want_seg,
                                              ld=max(rb.n_in, rb.n_out, 1))))
@@ -125,6 +123,53 @@ class plan_batch:
             rb._planned(side, res, job["want_order"])
             if job["want_segments"] and res["segments"] is None:
                 rb.pair_segments()              # chunked segment tables (MSMD_WGRAD_CHUNK_ROWS)
+
+
+class _TableSide:
+    """One neighbour table of a rulebook (nbr [K, n]: the output-stationary table of the
+    forward pass or of dgrad) and what the conv kernels derive from it, each computed once:
+    the tiling order of its rows (similar neighbour masks adjacent, tiles heaviest first),
+    the table in that order, and the stream-K work table per tile height."""
+
+    def __init__(self, nbr):
+        self.nbr = nbr
+        self._order = self._tiled = _UNSET
+        self._prefix = {}
+
+    def order(self):
+        if self._order is _UNSET:
+            self._order = K.rulebook_tiling(self.nbr, want_table=False)[0]
+        return self._order
+
+    def tiling(self):
+        """(table, row_order) the split-bf16 kernel tiles a pass by: the table in mask-sorted
+        tile order (column p belongs to row order[p]).
+        SubM rulebooks serve 8 launches per step (4 convs x forward/dgrad), a strided
+        conv's tables one launch each -- but those need it most: a stride-2 output
+        row has ~5 of the 27 offsets and its neighbours in linear order all have
+        different ones, so a 128-row tile in natural order walks every offset
+        (issued / useful work 5.4 forward, 8.1 backward on the bench workload;
+        1.8 / 1.0 sorted -- tools/order_sim.py).  The sort + permute (~100 us) runs
+        in the index pass, off the feature pass."""
+        if self._tiled is _UNSET:
+            self._order, self._tiled = K.rulebook_tiling(self.nbr)
+        return self._tiled, self._order
+
+    def prefix(self, rows):
+        """Stream-K work table of the tiling (K.tile_prefix) for tiles of `rows` rows
+        (K.split_tile_rows of the layer's width): with it every workgroup of the split
+        kernel takes the same share of the launch."""
+        if rows not in self._prefix:
+            self._prefix[rows] = K.tile_prefix(self.tiling()[0], rows)
+        return self._prefix[rows]
+
+    def take(self, res, keep_order):
+        """Adopt one K.rulebook_plan / K.rulebook_plan_many result for this table."""
+        if res["tiled"] is not None:
+            self._order, self._tiled = res["order"], res["tiled"]
+        elif keep_order and self._order is _UNSET:
+            self._order = res["order"]
+        self._prefix.update(res["prefix"])
 
 
 class IndiceData:
@@ -136,8 +181,9 @@ class IndiceData:
                  out_spatial_shape, ksize, stride, padding, dilation, algo=None):
         self.out_indices = out_indices
         self.indices = indices
-        self.nbr_fwd = nbr_fwd          # [K, n_out]
-        self.nbr_bwd = nbr_bwd          # [K, n_in]; None for SubM (fwd table, flipped)
+        self.fwd = _TableSide(nbr_fwd)          # [K, n_out]
+        # [K, n_in]; a SubM rulebook's dgrad reads the forward table (with flipped weights)
+        self.bwd = self.fwd if is_subm else _TableSide(nbr_bwd)
         self.is_subm = is_subm
         self.spatial_shape = spatial_shape
         self.out_spatial_shape = out_spatial_shape
@@ -146,15 +192,26 @@ class IndiceData:
         # True between build_rulebook() inside a plan_batch() and that context's exit: the
         # SubM table is allocated but not filled yet -- nothing may read it (table() checks)
         self.pending = False
-        self._pairs = None
+        self._pairs = None              # (forward table only, like the segment table)
         self._pair_segments = False     # not computed yet (None = chunking off)
-        self._order_fwd = None
-        self._order_bwd = None
-        self._tiled_fwd = None
-        self._tiled_bwd = None
-        self._prefix_fwd = {}
-        self._prefix_bwd = {}
         self._inverted = None
+
+    @property
+    def nbr_fwd(self):
+        return self.fwd.nbr
+
+    @nbr_fwd.setter
+    def nbr_fwd(self, nbr):
+        self.fwd.nbr = nbr
+
+    @property
+    def nbr_bwd(self):
+        return None if self.is_subm else self.bwd.nbr
+
+    @nbr_bwd.setter
+    def nbr_bwd(self, nbr):
+        assert not self.is_subm, "a SubM rulebook has no input-side table of its own"
+        self.bwd.nbr = nbr
 
     def inverted(self):
         """The rulebook of the inverse conv paired with this one (bug_fix/conv.py:350-362): the
@@ -207,144 +264,54 @@ class IndiceData:
     def prepare(self, need_grad, c_in=None, c_out=None):
         """Compute everything derived from the table now -- the pair lists when a
         weight gradient will be needed and, for a conv of c_in -> c_out channels,
-        the tiling order / tile-ordered table its kernels will ask for -- so that
-        the feature pass enqueues no index work and never waits on the host.
+        the tiling order / tile-ordered table its kernels will ask for (conv_needs) -- so
+        that the feature pass enqueues no index work and never waits on the host.
         Inside `plan_batch()` the work is only recorded; the batch's exit runs it for
         all tables together (K.rulebook_plan_many: one launch set)."""
+        kvol = self.nbr_fwd.shape[0]
+        needs = ConvNeeds(None, None, False, need_grad, False, 0) if c_in is None else \
+            conv_needs(c_in, c_out, kvol, self.n_in, self.n_out, need_grad, self.is_subm)
+        asks, want_segments = [a for a in (needs.fwd, needs.bwd) if a], needs.want_segments
         batch = getattr(_PLAN, "batch", None)
-        if c_in is not None:
-            from .functional import _use_split, _wants_order
-            kvol = self.nbr_fwd.shape[0]
-            # one library call for what the split kernels want from each table (tiling
-            # order, table in tile order, stream-K prefix, pair lists) instead of four:
-            # the index pass is bound by host time (DESIGN.md 8.5)
-            fwd_split = _use_split(c_in, c_out, kvol, self.n_in)
-            bwd_split = need_grad and _use_split(c_out, c_in, kvol, self.n_out)
-            if batch is not None and kvol <= 31 and self.n_out > 0 and self.n_in > 0:
-                wgs = need_grad and K.wgrad_split_supported(c_in, c_out)
-                fwd = batch.job(self, "fwd")
-                if fwd_split:
-                    fwd["tile_rows"].add(K.split_tile_rows(c_out))
-                elif _wants_order(c_in, c_out):
-                    fwd["want_order"] = True
-                fwd["want_pairs"] |= need_grad
-                fwd["want_segments"] |= wgs
-                if need_grad:
-                    side = fwd if self.is_subm else batch.job(self, "bwd")
-                    if bwd_split:
-                        side["tile_rows"].add(K.split_tile_rows(c_in))
-                    elif _wants_order(c_out, c_in):
-                        side["want_order"] = True
-                return self
-            if kvol <= 31 and self.n_out > 0 and self._tiled_fwd is None and \
-                    (fwd_split or (bwd_split and self.is_subm)):
-                rows = {K.split_tile_rows(c_out)} if fwd_split else set()
-                if bwd_split and self.is_subm:
-                    rows.add(K.split_tile_rows(c_in))
-                plan = K.rulebook_plan(self.nbr_fwd, rows, need_grad and self._pairs is None,
-                                       ld=max(self.n_in, self.n_out, 1))
-                self._order_fwd, self._tiled_fwd = (plan["order"],), (plan["tiled"],)
-                self._prefix_fwd.update(plan["prefix"])
-                if plan["pairs"] is not None:
-                    self._pairs = plan["pairs"]
-            if bwd_split and not self.is_subm and kvol <= 31 and self.n_in > 0 and \
-                    self._tiled_bwd is None:
-                plan = K.rulebook_plan(self.nbr_bwd, {K.split_tile_rows(c_in)})
-                self._order_bwd, self._tiled_bwd = (plan["order"],), (plan["tiled"],)
-                self._prefix_bwd.update(plan["prefix"])
-        elif batch is not None and need_grad and self.nbr_fwd.shape[0] <= 31 and \
+        if batch is not None and (asks or need_grad) and kvol <= 31 and \
                 self.n_out > 0 and self.n_in > 0:
-            batch.job(self, "fwd")["want_pairs"] = True
+            fwd = batch.job(self, "fwd")
+            fwd["want_pairs"] |= need_grad
+            fwd["want_segments"] |= want_segments
+            for side, kernel, rows in asks:
+                j = batch.job(self, side)
+                if kernel == "split":
+                    j["tile_rows"].add(rows)
+                j["want_order"] |= kernel == "ordered"
             return self
+        # one library call for what the split kernels want from each table (tiling
+        # order, table in tile order, stream-K prefix, pair lists) instead of four:
+        # the index pass is bound by host time (DESIGN.md 8.5)
+        for side in dict.fromkeys(a[0] for a in asks):
+            rows = {r for s, kernel, r in asks if s == side and kernel == "split"}
+            table = getattr(self, side)
+            if rows and kvol <= 31 and table.nbr.shape[1] > 0 and table._tiled is _UNSET:
+                want_pairs = side == "fwd" and need_grad and self._pairs is None
+                self._planned(side, K.rulebook_plan(table.nbr, rows, want_pairs,
+                                                    ld=max(self.n_in, self.n_out, 1)), False)
         if need_grad:
             self.pairs()
-            if c_in is not None and K.wgrad_split_supported(c_in, c_out):
+            if want_segments:
                 self.pair_segments()
-        if c_in is not None:
-            if _use_split(c_in, c_out, kvol, self.n_in):
-                self.prefix_fwd(c_out)
-            elif _wants_order(c_in, c_out):
-                self.order_fwd()
-            if need_grad:       # dgrad: the same kernel over the mirrored problem
-                if _use_split(c_out, c_in, kvol, self.n_out):
-                    self.prefix_bwd(c_in)
-                elif _wants_order(c_out, c_in):
-                    self.order_bwd()
+        for side, kernel, rows in asks:     # whatever is still missing (K > 31, empty tables)
+            if kernel == "split":
+                getattr(self, side).prefix(rows)
+            elif kernel == "ordered":
+                getattr(self, side).order()
         return self
 
     def _planned(self, side, res, keep_order):
-        """Take one K.rulebook_plan_many result (plan_batch.flush)."""
-        if side == "fwd":
-            if res["tiled"] is not None:
-                self._order_fwd, self._tiled_fwd = (res["order"],), (res["tiled"],)
-            elif keep_order and self._order_fwd is None:
-                self._order_fwd = (res["order"],)
-            self._prefix_fwd.update(res["prefix"])
-            if res["pairs"] is not None:
-                self._pairs = res["pairs"]
-            if res["segments"] is not None:
-                self._pair_segments = res["segments"]
-        else:
-            if res["tiled"] is not None:
-                self._order_bwd, self._tiled_bwd = (res["order"],), (res["tiled"],)
-            elif keep_order and self._order_bwd is None:
-                self._order_bwd = (res["order"],)
-            self._prefix_bwd.update(res["prefix"])
-
-    def order_fwd(self):
-        """Tiling order of the output rows (similar neighbour masks adjacent, tiles
-        heaviest first); for SubM the same order serves dgrad (its table is the
-        forward one mirrored)."""
-        if self._order_fwd is None:
-            self._order_fwd = (K.rulebook_tiling(self.nbr_fwd, want_table=False)[0],)
-        return self._order_fwd[0]
-
-    def order_bwd(self):
-        if self.is_subm:
-            return self.order_fwd()
-        if self._order_bwd is None:
-            self._order_bwd = (K.rulebook_tiling(self.nbr_bwd, want_table=False)[0],)
-        return self._order_bwd[0]
-
-    def tiling_fwd(self):
-        """(table, row_order) the split-bf16 kernel tiles the forward pass by: the
-        table in mask-sorted tile order (column p belongs to output row order[p]).
-        SubM rulebooks serve 8 launches per step (4 convs x forward/dgrad), a strided
-        conv's tables one launch each -- but those need it most: a stride-2 output
-        row has ~5 of the 27 offsets and its neighbours in linear order all have
-        different ones, so a 128-row tile in natural order walks every offset
-        (issued / useful work 5.4 forward, 8.1 backward on the bench workload;
-        1.8 / 1.0 sorted -- tools/order_sim.py).  The sort + permute (~100 us) runs
-        in the index pass, off the feature pass."""
-        if self._tiled_fwd is None:
-            order, table = K.rulebook_tiling(self.nbr_fwd)
-            self._order_fwd, self._tiled_fwd = (order,), (table,)
-        return self._tiled_fwd[0], self._order_fwd[0]
-
-    def prefix_fwd(self, c_out):
-        """Stream-K work table of the forward tiling (K.tile_prefix) for a conv with
-        c_out output channels (the kernel's tile size depends on the width): with it
-        every workgroup of the split kernel takes the same share of the launch."""
-        rows = K.split_tile_rows(c_out)
-        if rows not in self._prefix_fwd:
-            self._prefix_fwd[rows] = K.tile_prefix(self.tiling_fwd()[0], rows)
-        return self._prefix_fwd[rows]
-
-    def prefix_bwd(self, c_in):
-        if self.is_subm:
-            return self.prefix_fwd(c_in)
-        rows = K.split_tile_rows(c_in)
-        if rows not in self._prefix_bwd:
-            self._prefix_bwd[rows] = K.tile_prefix(self.tiling_bwd()[0], rows)
-        return self._prefix_bwd[rows]
-
-    def tiling_bwd(self):
-        if self.is_subm:      # forward table + flipped weights == backward table
-            return self.tiling_fwd()
-        if self._tiled_bwd is None:
-            order, table = K.rulebook_tiling(self.nbr_bwd)
-            self._order_bwd, self._tiled_bwd = (order,), (table,)
-        return self._tiled_bwd[0], self._order_bwd[0]
+        """Take one K.rulebook_plan / K.rulebook_plan_many result for the table of `side`."""
+        getattr(self, side).take(res, keep_order)
+        if res["pairs"] is not None:
+            self._pairs = res["pairs"]
+        if res.get("segments") is not None:
+            self._pair_segments = res["segments"]
 
 
 def build_rulebook(indices, batch_size, spatial_shape, ksize, stride, padding, dilation, subm,
@@ -381,6 +348,16 @@ def build_rulebook(indices, batch_size, spatial_shape, ksize, stride, padding, d
                                                            ksize, stride, padding)
     return IndiceData(out_idx, indices, nbr_fwd, nbr_bwd, False, list(spatial_shape),
                       list(out_shape), ksize, stride, padding, dilation, algo)
+
+
+def rulebook_key(indices, spatial_shape, ksize, stride, padding, dilation, subm,
+                 transposed=False, output_padding=(0, 0, 0)):
+    """Key of a rulebook in SparseConvTensor._rb_cache (see there)."""
+    key = (indices.data_ptr(), indices.shape[0], tuple(spatial_shape), tuple(ksize),
+           tuple(stride), tuple(padding), tuple(dilation), bool(subm))
+    if transposed:
+        key += ("transposed", tuple(int(v) for v in K._expand3(output_padding)))
+    return key
 
 
 def _changes_set_otherwise(layer):
@@ -462,10 +439,8 @@ class SparseConvTensor:
         # (b,mix,z,y,x: MSMDFusion.py:322-323); spconv asserts on ndim there too
         assert self.indices.shape[1] == 4, \
             f"sparse conv needs (b,z,y,x) indices, got {self.indices.shape[1]} columns"
-        ident = (self.indices.data_ptr(), self.indices.shape[0], tuple(self.spatial_shape),
-                 tuple(ksize), tuple(stride), tuple(padding), tuple(dilation), bool(subm))
-        if transposed:      # (the keys of the other geometries stay as seed_strided_chain writes them)
-            ident += ("transposed", tuple(int(v) for v in K._expand3(output_padding)))
+        ident = rulebook_key(self.indices, self.spatial_shape, ksize, stride, padding, dilation,
+                             subm, transposed, output_padding)
         hit = self._rb_cache.get(ident)
         # (an entry whose deferred fill failed is rebuilt, not handed out again)
         if hit is not None and hit.indices is self.indices and hit.nbr_fwd is not None:
@@ -474,6 +449,17 @@ class SparseConvTensor:
                             list(stride), list(padding), list(dilation), subm,
                             transposed=transposed, output_padding=K._expand3(output_padding))
         self._rb_cache[ident] = rb
+        return rb
+
+    def seed_rulebook(self, conv, out_indices, nbr_fwd, nbr_bwd, out_shape):
+        """File the rulebook of the plain strided `conv` over this tensor's voxel set -- its
+        output set and tables computed elsewhere (the chains that count several output sets
+        with one host read) -- where cached_rulebook() will look it up."""
+        rb = IndiceData(out_indices, self.indices, nbr_fwd, nbr_bwd, False,
+                        list(self.spatial_shape), list(out_shape), list(conv.kernel_size),
+                        list(conv.stride), list(conv.padding), list(conv.dilation), None)
+        self._rb_cache[rulebook_key(self.indices, self.spatial_shape, conv.kernel_size,
+                                    conv.stride, conv.padding, conv.dilation, False)] = rb
         return rb
 
     def seed_strided_chain(self, convs):
@@ -495,16 +481,12 @@ class SparseConvTensor:
                 any(d != 1 for c in strided for d in c.dilation):
             return
         geoms = [(list(c.kernel_size), list(c.stride), list(c.padding)) for c in strided]
-        idx, shape = self.indices, list(self.spatial_shape)
+        t = self
         for c, (out_idx, nbr_fwd, nbr_bwd, out_shape) in zip(
-                strided, K.rulebook_conv_chain(idx, self.batch_size, shape, geoms)):
-            ident = (idx.data_ptr(), idx.shape[0], tuple(shape), tuple(c.kernel_size),
-                     tuple(c.stride), tuple(c.padding), tuple(c.dilation), False)
-            self._rb_cache[ident] = IndiceData(out_idx, idx, nbr_fwd, nbr_bwd, False, list(shape),
-                                               list(out_shape), list(c.kernel_size),
-                                               list(c.stride), list(c.padding), list(c.dilation),
-                                               None)
-            idx, shape = out_idx, list(out_shape)
+                strided, K.rulebook_conv_chain(t.indices, t.batch_size, t.spatial_shape, geoms)):
+            t.seed_rulebook(c, out_idx, nbr_fwd, nbr_bwd, out_shape)
+            t = t.shadow_copy()         # (shares the cache) the next conv's input set
+            t.indices, t.spatial_shape = out_idx, list(out_shape)
 
     def plan(self, convs, need_grad, strided_outputs=None):
         """Index-only pre-pass: build (or fetch) the rulebook of every sparse
@@ -555,7 +537,6 @@ class SparseConvTensor:
     def dense(self, channels_first: bool = True):
         """[B,C,D,H,W] (structure.py:55-64); channels_last returns the permuted
         view of the same buffer."""
-        from .functional import dense as _dense
         assert self.indices.shape[1] == 4, \
             f"dense() needs (b,z,y,x) indices, got {self.indices.shape[1]} columns"
         out = _dense(self._features, self.indices, self.batch_size, self.spatial_shape)

@@ -6,6 +6,7 @@ spconv_ops.h:299); modules keep their parameter in spconv-2.x's KRSC layout
 and hand a permuted view in, so autograd maps the gradient back.
 """
 import os
+from collections import namedtuple
 
 import torch
 from torch.autograd import Function
@@ -31,19 +32,39 @@ def conv_planes():
 SPLIT_MAX_FEATURE_BYTES = 0xFFFFFF00
 
 
-def _use_split(c_in, c_out, kvol, n_in=0):
+def _use_split(c_in, c_out, kvol, n_in=0, planes=None):
     # c_in % 8 == 0 with a partial last k-block (the fusion stack's 80-channel layers)
     # included: 80->80 104 vs 114 us, 80->96 102 vs 135 since the split tiles (before
     # them the fp32 kernel won there, 118 vs 160).
     # Its gathers use 32-bit byte offsets: features beyond 4 GiB go the fp32 way.
-    return (conv_planes() in (1, 2, 3) and n_in * c_in * 4 < SPLIT_MAX_FEATURE_BYTES
-            and K.split_supported(c_in, c_out, kvol))
+    return ((conv_planes() if planes is None else planes) in (1, 2, 3)
+            and n_in * c_in * 4 < SPLIT_MAX_FEATURE_BYTES and K.split_supported(c_in, c_out, kvol))
 
 
-def _wants_order(c_in, c_out):
-    """The pipelined kernel (c_out >= 64, c_in % 16 == 0) profits from the
-    mask-sorted tiling order; the narrow layers ignore it."""
-    return c_out >= 64 and c_in % 16 == 0
+# fwd / bwd: (side, kernel, rows) -- the rulebook side whose table the pass reads, its kernel
+# ("split", or the fp32 one "ordered" by the tiling order or "plain") and the split kernel's
+# tile height; bwd is None without need_grad.  wgrad_split: the split wgrad kernel runs.
+ConvNeeds = namedtuple("ConvNeeds", "fwd bwd wgrad_split want_pairs want_segments planes")
+
+
+def conv_needs(c_in, c_out, kvol, n_in, n_out, need_grad, is_subm):
+    """The routing rules: which kernel each direction of a conv of c_in -> c_out runs, hence
+    what IndiceData.prepare() computes in the index pass and what the feature pass launches.
+    n_in / n_out: operand rows of the forward / dgrad kernel (the 4 GiB guard).  Evaluated at
+    every call: MSMD_CONV_PLANES may change between steps (planes: as read by this call)."""
+    planes = conv_planes()
+
+    def ask(side, ci, co, n):
+        if _use_split(ci, co, kvol, n, planes):
+            return side, "split", K.split_tile_rows(co)
+        # the pipelined fp32 kernel (c_out >= 64, c_in % 16 == 0) profits from the
+        # mask-sorted tiling order; the narrow layers ignore it
+        return side, "ordered" if co >= 64 and ci % 16 == 0 else "plain", None
+    # dgrad: the same kernel over the mirrored problem (SubM: over the forward table)
+    bwd = ask("fwd" if is_subm else "bwd", c_out, c_in, n_out) if need_grad else None
+    wgs = bool(need_grad) and K.wgrad_split_supported(c_in, c_out)
+    return ConvNeeds(ask("fwd", c_in, c_out, n_in), bwd, wgs and planes in (1, 2, 3),
+                     bool(need_grad), wgs, planes)
 
 
 _F32_TILE_COUNTS = (12, 8, 6, 5, 4, 3, 2, 1)    # instantiations of msmd_spconv_fwd_f32
@@ -177,11 +198,13 @@ def _conv_forward(features, weight, rb, krsc, want_dgrad, bn_stats=False):
     """-> (out, packed W^T for dgrad | None[, BN partials | None when bn_stats])."""
     c_in, c_out = (weight.shape[-1], weight.shape[0]) if krsc else weight.shape[1:]
     rb.check_ready()
-    if _use_split(c_in, c_out, rb.nbr_fwd.shape[0], features.shape[0]):
-        np_ = conv_planes()
+    needs = conv_needs(c_in, c_out, rb.nbr_fwd.shape[0], features.shape[0], rb.n_out, want_dgrad,
+                       rb.is_subm)
+    _, kernel, rows = needs.fwd
+    if kernel == "split":
+        np_ = needs.planes
         packed_t = None
-        # dgrad will want W^T packed too
-        want_t = want_dgrad and _use_split(c_out, c_in, rb.nbr_fwd.shape[0], rb.n_out)
+        want_t = want_dgrad and needs.bwd[1] == "split"     # dgrad will want W^T packed too
         if isinstance(weight, torch.nn.Parameter):
             packed, packed_t = _packed_parameter(weight, np_, krsc, want_t)
             packed_t = packed_t if want_t else None
@@ -189,13 +212,13 @@ def _conv_forward(features, weight, rb, krsc, want_dgrad, bn_stats=False):
             packed, packed_t = K.pack_weight_split_pair(weight, np_, krsc=krsc)
         else:
             packed = K.pack_weight_split(weight, np_, krsc=krsc)
-        table, order = rb.tiling_fwd()
+        table, order = rb.fwd.tiling()
         res = K.conv_forward_split(features, packed, table, rb.n_out, c_out, np_,
-                                   row_order=order, tile_prefix=rb.prefix_fwd(c_out),
+                                   row_order=order, tile_prefix=rb.fwd.prefix(rows),
                                    bn_stats=bn_stats)
         return (res[0], packed_t, res[1]) if bn_stats else (res, packed_t)
     out = _conv_f32(features, weight, krsc, False, rb.nbr_fwd, rb.n_out,
-                    row_order=rb.order_fwd() if _wants_order(c_in, c_out) else None)
+                    row_order=rb.fwd.order() if kernel == "ordered" else None)
     return (out, None, None) if bn_stats else (out, None)
 
 
@@ -221,34 +244,35 @@ class _SparseConvFunction(Function):
         c_in, c_out = (weight.shape[-1], weight.shape[0]) if krsc else weight.shape[1:]
         grad_out = grad_out.contiguous()
         d_feat = d_w = None
+        needs = conv_needs(c_in, c_out, rb.nbr_fwd.shape[0], features.shape[0],
+                           grad_out.shape[0], True, rb.is_subm)
         if ctx.needs_input_grad[1]:
             # (rounds 1-2 could put wgrad on a side stream, MSMD_WGRAD_STREAM=1: its thousands
             # of short workgroups filled the CUs the persistent dgrad kernel left idle in its
             # tail, +2-3 %.  The whole-block kernel is one 144 KB workgroup per CU: next to
             # dgrad it measured -1 % on the LC path and -3 % on configs[1]; removed.)
             pairs, num = rb.pairs()     # (cached; built on this stream if not yet)
-            if conv_planes() in (1, 2, 3) and K.wgrad_split_supported(c_in, c_out):
-                d_w = K.conv_wgrad_split(features, grad_out, pairs, num, conv_planes(),
+            if needs.wgrad_split:
+                d_w = K.conv_wgrad_split(features, grad_out, pairs, num, needs.planes,
                                          krsc_shape=weight.shape if krsc else None,
                                          segments=rb.pair_segments())
             else:
                 d_w = K.conv_wgrad(features, grad_out, pairs, num,
                                    krsc_shape=weight.shape if krsc else None)
-        if ctx.needs_input_grad[0] and _use_split(c_out, c_in, rb.nbr_fwd.shape[0],
-                                                  grad_out.shape[0]):
-            np_ = conv_planes()
-            packed_t = ctx.packed_t if ctx.packed_t is not None else \
-                K.pack_weight_split(weight, np_, transpose=True, krsc=krsc)
-            table, order = rb.tiling_bwd()
-            d_feat = K.conv_forward_split(grad_out, packed_t, table, rb.n_in, c_in, np_,
-                                          weight_flip=rb.is_subm, row_order=order,
-                                          tile_prefix=rb.prefix_bwd(c_in))
-        elif ctx.needs_input_grad[0]:
-            order = rb.order_bwd() if _wants_order(c_out, c_in) else None
-            # SubM: forward table + flipped weights == backward table
-            d_feat = _conv_f32(grad_out, weight, krsc, True,
-                               rb.nbr_fwd if rb.is_subm else rb.nbr_bwd, rb.n_in,
-                               weight_flip=rb.is_subm, row_order=order)
+        if ctx.needs_input_grad[0]:
+            side, kernel, rows = needs.bwd
+            side = getattr(rb, side)
+            if kernel == "split":
+                packed_t = ctx.packed_t if ctx.packed_t is not None else \
+                    K.pack_weight_split(weight, needs.planes, transpose=True, krsc=krsc)
+                table, order = side.tiling()
+                d_feat = K.conv_forward_split(grad_out, packed_t, table, rb.n_in, c_in,
+                                              needs.planes, weight_flip=rb.is_subm,
+                                              row_order=order, tile_prefix=side.prefix(rows))
+            else:
+                d_feat = _conv_f32(grad_out, weight, krsc, True, side.nbr, rb.n_in,
+                                   weight_flip=rb.is_subm,
+                                   row_order=side.order() if kernel == "ordered" else None)
         return d_feat, d_w, None, None, None
 
 

@@ -404,16 +404,18 @@ def test_plan_batch_equals_table_by_table_planning(dev, monkeypatch):
     planned = 0
     for got, rb in zip(rbs_b, rbs_s):
         assert got is not rb and torch.equal(got.nbr_fwd, rb.nbr_fwd)
-        for f in ("_order_fwd", "_tiled_fwd", "_order_bwd", "_tiled_bwd"):
-            a, b = getattr(got, f), getattr(rb, f)
-            assert (a is None) == (b is None), f
-            if a is not None:
-                assert torch.equal(a[0], b[0]), f
-                planned += 1
-        for pa, pb in ((got._prefix_fwd, rb._prefix_fwd), (got._prefix_bwd, rb._prefix_bwd)):
-            assert set(pa) == set(pb)
-            for h in pa:
-                assert torch.equal(pa[h], pb[h])
+        assert (got.bwd is got.fwd) == (rb.bwd is rb.fwd) == rb.is_subm
+        for side in ("fwd", "bwd"):
+            sa, sb = getattr(got, side), getattr(rb, side)
+            for f in ("_order", "_tiled"):
+                a, b = getattr(sa, f), getattr(sb, f)
+                assert (a is core._UNSET) == (b is core._UNSET), (side, f)
+                if a is not core._UNSET:
+                    assert torch.equal(a, b), (side, f)
+                    planned += side == "fwd" or not rb.is_subm      # (a SubM table counts once)
+            assert set(sa._prefix) == set(sb._prefix)
+            for h in sa._prefix:
+                assert torch.equal(sa._prefix[h], sb._prefix[h])
         assert (got._pairs is None) == (rb._pairs is None)
         if rb._pairs is not None:
             assert torch.equal(got._pairs[0], rb._pairs[0])

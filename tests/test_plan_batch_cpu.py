@@ -18,8 +18,8 @@ class _FakeRb:
         self.n_in = self.n_out = n
         self._pairs = None
         self._pair_segments = False
-        self._order_fwd = self._order_bwd = self._tiled_fwd = self._tiled_bwd = None
-        self._prefix_fwd, self._prefix_bwd = {}, {}
+        self.fwd = core._TableSide(self.nbr_fwd)
+        self.bwd = self.fwd if subm else core._TableSide(self.nbr_bwd)
         self.planned = []
 
     def _planned(self, side, res, keep_order):
