@@ -2,18 +2,12 @@
 // LiDAR / virtual-point modality split.  HBM-bound permutation / set kernels.
 #include "common.hpp"
 #include "scan.hpp"
+#include "voxel_set.hpp"
 
 namespace msmd {
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t cell_of(int4 r, const int* s) {
-  return (((uint32_t)r.x * s[0] + r.y) * s[1] + r.z) * s[2] + r.w;
-}
-struct Shape3 {
-  int s[3];
-};
 
 // ---------------------------------------------------------------- dense ----
 // structure.py:55-64 does zero-fill + scatter to [B,D,H,W,C] + a full permute
@@ -69,12 +63,6 @@ size_t dense_smem(int c) {
 }
 
 // ----------------------------------------------------------- sparse_add ----
-__global__ __launch_bounds__(256) void mark_rows(const int32_t* __restrict__ idx, int n, Shape3 sh,
-                                                 uint32_t* bits) {
-  int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) bitmap_set(bits, cell_of(((const int4*)idx)[i], sh.s));
-}
-
 __global__ __launch_bounds__(256) void add_rows(const float* __restrict__ feat,
                                                 const int32_t* __restrict__ idx, int n, int c,
                                                 Shape3 sh, const uint32_t* __restrict__ bits,
@@ -87,7 +75,7 @@ __global__ __launch_bounds__(256) void add_rows(const float* __restrict__ feat,
   const int i = (int)(t >> 4), sub = (int)(t & 15);
   if (i >= n) return;
   int4 r = ((const int4*)idx)[i];
-  int o = bitmap_rank(bits, prefix, cell_of(r, sh.s));
+  int o = bitmap_rank(bits, prefix, cell_id(r.x, r.y, r.z, r.w, sh.s));
   if (o >= n_out) return;
   if (sub == 0) {
     ((int4*)out_idx)[o] = r;
@@ -130,7 +118,7 @@ __global__ __launch_bounds__(256) void split_rows(const int32_t* __restrict__ id
   int m = 0, b = -1;
   if (i < n) {
     const int4 r = ((const int4*)idx)[i];
-    uint32_t cell = cell_of(r, sh.s);
+    uint32_t cell = cell_id(r.x, r.y, r.z, r.w, sh.s);
     m = bitmap_test(both, cell);
     b = r.x;
     mix[i] = m;
@@ -150,33 +138,6 @@ __global__ __launch_bounds__(256) void split_rows(const int32_t* __restrict__ id
   }
 }
 
-struct SetWs {
-  uint32_t *bits, *bits2;
-  int *prefix, *tiles;
-  size_t words;
-};
-template <typename A>
-void carve_set(A& a, SetWs* w, int batch, const int* shape, bool two) {
-  size_t cells = (size_t)batch * shape[0] * shape[1] * shape[2];
-  size_t words = (cells + 31) / 32;
-  uint32_t* b0 = a.template take<uint32_t>(words);
-  uint32_t* b1 = two ? a.template take<uint32_t>(words) : nullptr;
-  int* pf = a.template take<int>(words);
-  int* tl = a.template take<int>(scan_num_tiles((long)words) + 1);
-  if (w) *w = SetWs{b0, b1, pf, tl, words};
-}
-
-int check_grid(int batch, const int* shape, Shape3* sh) {
-  if (batch < 1 || !shape) return MSMD_ERR_INVALID_ARG;
-  double cells = batch;
-  for (int i = 0; i < 3; ++i) {
-    if (shape[i] < 1) return MSMD_ERR_INVALID_ARG;
-    sh->s[i] = shape[i];
-    cells *= shape[i];
-  }
-  return cells >= 4294967295.0 ? MSMD_ERR_RANGE : MSMD_OK;
-}
-
 }  // namespace
 }  // namespace msmd
 
@@ -186,7 +147,7 @@ MSMD_EXPORT int msmd_dense_scatter_f32(const float* feat, const int32_t* indices
                                        int batch_size, const int* spatial_shape, float* out,
                                        msmd_stream_t stream) {
   Shape3 sh;
-  int rc = check_grid(batch_size, spatial_shape, &sh);
+  int rc = check_grid(batch_size, spatial_shape, sh.s);
   if (rc) return rc;
   if (n < 0 || c < 1 || !out || (n > 0 && (!feat || !indices))) return MSMD_ERR_INVALID_ARG;
   size_t smem = dense_smem(c);
@@ -208,7 +169,7 @@ MSMD_EXPORT int msmd_dense_gather_f32(const float* dense, const int32_t* indices
                                       int batch_size, const int* spatial_shape, float* feat,
                                       msmd_stream_t stream) {
   Shape3 sh;
-  int rc = check_grid(batch_size, spatial_shape, &sh);
+  int rc = check_grid(batch_size, spatial_shape, sh.s);
   if (rc) return rc;
   if (n < 0 || c < 1 || (n > 0 && (!feat || !indices || !dense))) return MSMD_ERR_INVALID_ARG;
   if (n == 0) return MSMD_OK;
@@ -223,9 +184,7 @@ MSMD_EXPORT int msmd_dense_gather_f32(const float* dense, const int32_t* indices
 }
 
 MSMD_EXPORT size_t msmd_sparse_add_workspace_bytes(int batch_size, const int* spatial_shape) {
-  ArenaSize a;
-  carve_set(a, (SetWs*)nullptr, batch_size, spatial_shape, false);
-  return a.off;
+  return set_workspace_bytes(batch_size, spatial_shape);
 }
 
 MSMD_EXPORT int msmd_sparse_add_count(const int32_t* idx_a, int n_a, const int32_t* idx_b,
@@ -233,22 +192,17 @@ MSMD_EXPORT int msmd_sparse_add_count(const int32_t* idx_a, int n_a, const int32
                                       int32_t* n_out, void* workspace, size_t workspace_bytes,
                                       msmd_stream_t stream) {
   Shape3 sh;
-  int rc = check_grid(batch_size, spatial_shape, &sh);
+  int rc = check_grid(batch_size, spatial_shape, sh.s);
   if (rc) return rc;
   if (n_a < 0 || n_b < 0 || !n_out) return MSMD_ERR_INVALID_ARG;
-  Arena a(workspace, workspace_bytes);
   SetWs w;
-  carve_set(a, &w, batch_size, spatial_shape, false);
-  if (!a.ok()) return MSMD_ERR_WORKSPACE;
+  if (!carve_set_at(workspace, workspace_bytes, &w, batch_size, spatial_shape))
+    return MSMD_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   hipMemsetAsync(w.bits, 0, sizeof(uint32_t) * w.words, st);
-  if (n_a > 0)
-    MSMD_LAUNCH(mark_rows, dim3(ceil_div(n_a, 256)), dim3(256), 0, st, idx_a, n_a, sh,
-                       w.bits);
-  if (n_b > 0)
-    MSMD_LAUNCH(mark_rows, dim3(ceil_div(n_b, 256)), dim3(256), 0, st, idx_b, n_b, sh,
-                       w.bits);
-  device_scan(PopcCount{w.bits}, StorePrefix{w.prefix}, (int)w.words, w.tiles, n_out, -1, st);
+  mark_rows(idx_a, n_a, sh, w.bits, st);
+  mark_rows(idx_b, n_b, sh, w.bits, st);
+  scan_set(w, n_out, st);
   return launch_status();
 }
 
@@ -259,16 +213,15 @@ MSMD_EXPORT int msmd_sparse_add_fill(const float* feat_a, const int32_t* idx_a, 
                                      int32_t* map_b, void* workspace, size_t workspace_bytes,
                                      msmd_stream_t stream) {
   Shape3 sh;
-  int rc = check_grid(batch_size, spatial_shape, &sh);
+  int rc = check_grid(batch_size, spatial_shape, sh.s);
   if (rc) return rc;
   // c == 0: index-only pass (out_indices + maps; no feature pointer is touched)
   if (n_a < 0 || n_b < 0 || c < 0 || n_out < 0 ||
       (n_out > 0 && (!out_indices || (c > 0 && !out_feat))))
     return MSMD_ERR_INVALID_ARG;
-  Arena a(workspace, workspace_bytes);
   SetWs w;
-  carve_set(a, &w, batch_size, spatial_shape, false);
-  if (!a.ok()) return MSMD_ERR_WORKSPACE;
+  if (!carve_set_at(workspace, workspace_bytes, &w, batch_size, spatial_shape))
+    return MSMD_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   if (n_out > 0 && c > 0) hipMemsetAsync(out_feat, 0, sizeof(float) * (size_t)n_out * c, st);
   if (n_a > 0)
@@ -298,9 +251,7 @@ MSMD_EXPORT int msmd_sparse_add_rows(const float* feat_a, const int32_t* map_a, 
 }
 
 MSMD_EXPORT size_t msmd_modality_split_workspace_bytes(int batch_size, const int* spatial_shape) {
-  ArenaSize a;
-  carve_set(a, (SetWs*)nullptr, batch_size, spatial_shape, true);
-  return a.off;
+  return set_workspace_bytes(batch_size, spatial_shape, true);
 }
 
 static int modality_split_impl(const int32_t* idx_3d, int n3, const int32_t* idx_2d, int n2,
@@ -309,26 +260,21 @@ static int modality_split_impl(const int32_t* idx_3d, int n3, const int32_t* idx
                                int32_t* n_mixed, int32_t* stats, void* workspace,
                                size_t workspace_bytes, msmd_stream_t stream) {
   Shape3 sh;
-  int rc = check_grid(batch_size, spatial_shape, &sh);
+  int rc = check_grid(batch_size, spatial_shape, sh.s);
   if (rc) return rc;
   if (n3 < 0 || n2 < 0 || !n_mixed) return MSMD_ERR_INVALID_ARG;
-  Arena a(workspace, workspace_bytes);
   SetWs w;
-  carve_set(a, &w, batch_size, spatial_shape, true);
-  if (!a.ok()) return MSMD_ERR_WORKSPACE;
+  if (!carve_set_at(workspace, workspace_bytes, &w, batch_size, spatial_shape, true))
+    return MSMD_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   // (the two bitmaps lie next to each other in the arena: one fill)
   hipMemsetAsync(w.bits, 0, (size_t)((char*)(w.bits2 + w.words) - (char*)w.bits), st);
   if (stats) hipMemsetAsync(stats, 0, sizeof(int32_t) * 4 * batch_size, st);
-  if (n3 > 0)
-    MSMD_LAUNCH(mark_rows, dim3(ceil_div(n3, 256)), dim3(256), 0, st, idx_3d, n3, sh,
-                       w.bits);
-  if (n2 > 0)
-    MSMD_LAUNCH(mark_rows, dim3(ceil_div(n2, 256)), dim3(256), 0, st, idx_2d, n2, sh,
-                       w.bits2);
+  mark_rows(idx_3d, n3, sh, w.bits, st);
+  mark_rows(idx_2d, n2, sh, w.bits2, st);
   MSMD_LAUNCH(and_words, dim3(ceil_div((long)w.words, 256)), dim3(256), 0, st, w.bits,
                      w.bits2, w.words);
-  device_scan(PopcCount{w.bits}, StorePrefix{w.prefix}, (int)w.words, w.tiles, n_mixed, -1, st);
+  scan_set(w, n_mixed, st);
   const int cap = n3 < n2 ? n3 : n2;
   // stats = [3D plain | 3D mixed | 2D plain | 2D mixed], batch_size entries each
   if (n3 > 0)

@@ -22,6 +22,7 @@
 // the reference configs use it), anything else returns MSMD_ERR_UNSUPPORTED.
 #include "common.hpp"
 #include "scan.hpp"
+#include "voxel_set.hpp"
 
 #include <stdlib.h>
 
@@ -33,10 +34,6 @@ struct Geom {
   int ks[3], st[3], pd[3];
   int kvol;
 };
-
-__device__ __forceinline__ uint32_t cell_id(int b, int z, int y, int x, const int* s) {
-  return (((uint32_t)b * s[0] + z) * s[1] + y) * s[2] + x;
-}
 
 // ---------------------------------------------------------------- SubM ----
 __global__ __launch_bounds__(256) void subm_insert(const int32_t* __restrict__ idx, int n,
@@ -561,21 +558,18 @@ __global__ __launch_bounds__(kScanBlock) void pairs_apply_kernel(
 
 int check_geom(const int* shape, const int* ks, const int* st, const int* pd, int batch,
                Geom* g) {
-  if (!shape || !ks || batch < 1) return MSMD_ERR_INVALID_ARG;
-  double cells = batch;
+  const int grid = check_grid(batch, shape, g->shape);
+  if (grid == MSMD_ERR_INVALID_ARG || !ks) return MSMD_ERR_INVALID_ARG;
   g->kvol = 1;
   for (int i = 0; i < 3; ++i) {
-    g->shape[i] = shape[i];
     g->ks[i] = ks[i];
     g->st[i] = st ? st[i] : 1;
     g->pd[i] = pd ? pd[i] : ks[i] / 2;  // SubM: spconv_ops.h:76-79
-    if (shape[i] < 1 || ks[i] < 1 || g->st[i] < 1 || g->pd[i] < 0) return MSMD_ERR_INVALID_ARG;
-    cells *= shape[i];
+    if (ks[i] < 1 || g->st[i] < 1 || g->pd[i] < 0) return MSMD_ERR_INVALID_ARG;
     g->kvol *= ks[i];
   }
   if (g->kvol > 4096) return MSMD_ERR_UNSUPPORTED;  // spconv_ops.h:51
-  if (cells >= 4294967295.0) return MSMD_ERR_RANGE;
-  return MSMD_OK;
+  return grid;                                      // (too many cells: MSMD_ERR_RANGE)
 }
 
 }  // namespace
@@ -965,29 +959,81 @@ MSMD_EXPORT int msmd_rulebook_subm3d_many(const msmd_subm_desc* descs, int n_des
   return launch_status();
 }
 
-// --------------------------------------------------------------- strided ---
+// --------------------------------------------------- strided / transposed ---
+// An output set is a voxel set of the OUTPUT grid (voxel_set.hpp): its workspace is the one
+// set's, whoever carves it.
 namespace {
-struct ConvWs {
-  uint32_t* bits;
-  int* prefix;
-  int* tiles;
-  size_t words;
-};
-template <typename A>
-void carve_conv(A& a, ConvWs* w, int batch, const int* out_shape) {
-  size_t cells = (size_t)batch * out_shape[0] * out_shape[1] * out_shape[2];
-  size_t words = (cells + 31) / 32;
-  uint32_t* b = a.template take<uint32_t>(words);
-  int* p = a.template take<int>(words);
-  int* t = a.template take<int>(scan_num_tiles((long)words) + 1);
-  if (w) *w = ConvWs{b, p, t, words};
+inline size_t region_bytes(int batch, const int* shape) {
+  return align_up(set_workspace_bytes(batch, shape));
+}
+
+// One output set: clear, mark, scan.  Marked from the input rows, or -- a level of a chain,
+// whose input set is the set counted just before -- from that set's bitmap `from` over the
+// grid from_shape.
+template <bool kTransposed>
+void count_level(const int32_t* indices, int n, const SetWs* from, const int* from_shape,
+                 int batch, const Geom& g, const SetWs& w, int32_t* count, hipStream_t st) {
+  hipMemsetAsync(w.bits, 0, sizeof(uint32_t) * w.words, st);
+  if (!from) {
+    if (n > 0)
+      MSMD_LAUNCH(conv_mark<kTransposed>, dim3(ceil_div(n, 256), g.kvol), dim3(256), 0, st,
+                  indices, n, g, w.bits);
+  } else {
+    const long oc = (long)batch * g.shape[0] * g.shape[1] * g.shape[2];
+    if (oc <= kConvGatherCells)
+      MSMD_LAUNCH(conv_mark_gather, dim3(ceil_div(oc, 256)), dim3(256), 0, st,
+                  (const uint32_t*)from->bits, from_shape[0], from_shape[1], from_shape[2], g, oc,
+                  w.bits);
+    else
+      MSMD_LAUNCH(conv_mark_from_bits, dim3(ceil_div((long)from->words, 256)), dim3(256), 0, st,
+                  (const uint32_t*)from->bits, (long)from->words, from_shape[0], from_shape[1],
+                  from_shape[2], g, w.bits);
+  }
+  scan_set(w, count, st);
+}
+
+template <bool kTransposed>
+int count_strided(const int32_t* indices, int n, int batch_size, const int* out_shape,
+                  const int* ksize, const int* stride, const int* padding, int32_t* n_out,
+                  void* workspace, size_t workspace_bytes, msmd_stream_t stream) {
+  Geom g;
+  if (!stride || !padding || !n_out) return MSMD_ERR_INVALID_ARG;
+  int rc = check_geom(out_shape, ksize, stride, padding, batch_size, &g);
+  if (rc) return rc;
+  if (n < 0 || (n > 0 && !indices)) return MSMD_ERR_INVALID_ARG;
+  SetWs w;
+  if (!carve_set_at(workspace, workspace_bytes, &w, batch_size, out_shape))
+    return MSMD_ERR_WORKSPACE;
+  count_level<kTransposed>(indices, n, nullptr, nullptr, batch_size, g, w, n_out,
+                           (hipStream_t)stream);
+  return launch_status();
+}
+
+template <bool kTransposed>
+int fill_strided(const int32_t* indices, int n, int batch_size, const int* out_shape,
+                 const int* ksize, const int* stride, const int* padding, int n_out,
+                 int32_t* out_indices, int32_t* nbr_fwd, int32_t* nbr_bwd, void* workspace,
+                 size_t workspace_bytes, msmd_stream_t stream) {
+  Geom g;
+  if (!stride || !padding) return MSMD_ERR_INVALID_ARG;
+  int rc = check_geom(out_shape, ksize, stride, padding, batch_size, &g);
+  if (rc) return rc;
+  if (n < 0 || n_out < 0 || (n_out > 0 && (!out_indices || !nbr_fwd)))
+    return MSMD_ERR_INVALID_ARG;
+  SetWs w;
+  if (!carve_set_at(workspace, workspace_bytes, &w, batch_size, out_shape))
+    return MSMD_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  if (n_out > 0) hipMemsetAsync(nbr_fwd, 0xFF, sizeof(int32_t) * (size_t)g.kvol * n_out, st);
+  if (n > 0)
+    MSMD_LAUNCH(conv_fill<kTransposed>, dim3(ceil_div(n, 256), g.kvol), dim3(256), 0, st, indices,
+                n, g, w.bits, w.prefix, n_out, out_indices, nbr_fwd, nbr_bwd);
+  return launch_status();
 }
 }  // namespace
 
 MSMD_EXPORT size_t msmd_rulebook_conv_workspace_bytes(int batch_size, const int* out_shape) {
-  ArenaSize a;
-  carve_conv(a, (ConvWs*)nullptr, batch_size, out_shape);
-  return a.off;
+  return set_workspace_bytes(batch_size, out_shape);
 }
 
 MSMD_EXPORT int msmd_rulebook_conv3d_count(const int32_t* indices, int n, int batch_size,
@@ -995,22 +1041,40 @@ MSMD_EXPORT int msmd_rulebook_conv3d_count(const int32_t* indices, int n, int ba
                                            const int* stride, const int* padding,
                                            int32_t* n_out, void* workspace,
                                            size_t workspace_bytes, msmd_stream_t stream) {
-  Geom g;
-  if (!stride || !padding || !n_out) return MSMD_ERR_INVALID_ARG;
-  int rc = check_geom(out_shape, ksize, stride, padding, batch_size, &g);
-  if (rc) return rc;
-  if (n < 0 || (n > 0 && !indices)) return MSMD_ERR_INVALID_ARG;
-  Arena a(workspace, workspace_bytes);
-  ConvWs w;
-  carve_conv(a, &w, batch_size, out_shape);
-  if (!a.ok()) return MSMD_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  hipMemsetAsync(w.bits, 0, sizeof(uint32_t) * w.words, st);
-  if (n > 0)
-    MSMD_LAUNCH(conv_mark<false>, dim3(ceil_div(n, 256), g.kvol), dim3(256), 0, st, indices, n, g,
-                       w.bits);
-  device_scan(PopcCount{w.bits}, StorePrefix{w.prefix}, (int)w.words, w.tiles, n_out, -1, st);
-  return launch_status();
+  return count_strided<false>(indices, n, batch_size, out_shape, ksize, stride, padding, n_out,
+                              workspace, workspace_bytes, stream);
+}
+
+MSMD_EXPORT int msmd_rulebook_conv3d_fill(const int32_t* indices, int n, int batch_size,
+                                          const int* out_shape, const int* ksize,
+                                          const int* stride, const int* padding, int n_out,
+                                          int32_t* out_indices, int32_t* nbr_fwd,
+                                          int32_t* nbr_bwd, void* workspace,
+                                          size_t workspace_bytes, msmd_stream_t stream) {
+  return fill_strided<false>(indices, n, batch_size, out_shape, ksize, stride, padding, n_out,
+                             out_indices, nbr_fwd, nbr_bwd, workspace, workspace_bytes, stream);
+}
+
+// Transposed: getIndicePairsDeConv (geometry.h:196-245) on the same bitmap + rank scheme: the
+// output grid is the deconv size, (in - 1) * s - 2p + k + output_padding (ops.py:33-43), which
+// the caller passes as out_shape; the workspace is msmd_rulebook_conv_workspace_bytes of it.
+MSMD_EXPORT int msmd_rulebook_deconv3d_count(const int32_t* indices, int n, int batch_size,
+                                             const int* out_shape, const int* ksize,
+                                             const int* stride, const int* padding,
+                                             int32_t* n_out, void* workspace,
+                                             size_t workspace_bytes, msmd_stream_t stream) {
+  return count_strided<true>(indices, n, batch_size, out_shape, ksize, stride, padding, n_out,
+                             workspace, workspace_bytes, stream);
+}
+
+MSMD_EXPORT int msmd_rulebook_deconv3d_fill(const int32_t* indices, int n, int batch_size,
+                                            const int* out_shape, const int* ksize,
+                                            const int* stride, const int* padding, int n_out,
+                                            int32_t* out_indices, int32_t* nbr_fwd,
+                                            int32_t* nbr_bwd, void* workspace,
+                                            size_t workspace_bytes, msmd_stream_t stream) {
+  return fill_strided<true>(indices, n, batch_size, out_shape, ksize, stride, padding, n_out,
+                            out_indices, nbr_fwd, nbr_bwd, workspace, workspace_bytes, stream);
 }
 
 // A chain of strided convs (each one's input set = the previous one's output set, as in
@@ -1023,8 +1087,7 @@ MSMD_EXPORT size_t msmd_rulebook_conv_chain_workspace_bytes(int batch_size, int 
                                                             const int* out_shapes) {
   if (levels < 1 || !out_shapes) return 0;
   size_t total = 0;
-  for (int l = 0; l < levels; ++l)
-    total += align_up(msmd_rulebook_conv_workspace_bytes(batch_size, out_shapes + 3 * l));
+  for (int l = 0; l < levels; ++l) total += region_bytes(batch_size, out_shapes + 3 * l);
   return total;
 }
 
@@ -1042,114 +1105,22 @@ MSMD_EXPORT int msmd_rulebook_conv3d_count_chain(const int32_t* indices, int n, 
     return MSMD_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   char* base = (char*)workspace;
-  ConvWs prev{};
+  SetWs prev{};
   const int* prev_shape = nullptr;
   for (int l = 0; l < levels; ++l) {
+    const int* shape = out_shapes + 3 * l;
     Geom g;
-    int rc = check_geom(out_shapes + 3 * l, ksizes + 3 * l, strides + 3 * l, paddings + 3 * l,
-                        batch_size, &g);
+    int rc = check_geom(shape, ksizes + 3 * l, strides + 3 * l, paddings + 3 * l, batch_size, &g);
     if (rc) return rc;
-    const size_t bytes = align_up(msmd_rulebook_conv_workspace_bytes(batch_size, out_shapes + 3 * l));
-    Arena a(base, bytes);
-    ConvWs w;
-    carve_conv(a, &w, batch_size, out_shapes + 3 * l);
-    if (!a.ok()) return MSMD_ERR_WORKSPACE;
-    hipMemsetAsync(w.bits, 0, sizeof(uint32_t) * w.words, st);
-    if (l == 0) {
-      if (n > 0)
-        MSMD_LAUNCH(conv_mark<false>, dim3(ceil_div(n, 256), g.kvol), dim3(256), 0, st, indices, n, g,
-                    w.bits);
-    } else {
-      const long oc = (long)batch_size * g.shape[0] * g.shape[1] * g.shape[2];
-      if (oc <= kConvGatherCells)
-        MSMD_LAUNCH(conv_mark_gather, dim3(ceil_div(oc, 256)), dim3(256), 0, st,
-                    (const uint32_t*)prev.bits, prev_shape[0], prev_shape[1], prev_shape[2], g, oc,
-                    w.bits);
-      else
-        MSMD_LAUNCH(conv_mark_from_bits, dim3(ceil_div((long)prev.words, 256)), dim3(256), 0, st,
-                    (const uint32_t*)prev.bits, (long)prev.words, prev_shape[0], prev_shape[1],
-                    prev_shape[2], g, w.bits);
-    }
-    device_scan(PopcCount{w.bits}, StorePrefix{w.prefix}, (int)w.words, w.tiles, n_out + l, -1, st);
+    const size_t bytes = region_bytes(batch_size, shape);
+    SetWs w;
+    if (!carve_set_at(base, bytes, &w, batch_size, shape)) return MSMD_ERR_WORKSPACE;
+    count_level<false>(indices, n, l ? &prev : nullptr, prev_shape, batch_size, g, w, n_out + l,
+                       st);
     prev = w;
-    prev_shape = out_shapes + 3 * l;
+    prev_shape = shape;
     base += bytes;
   }
-  return launch_status();
-}
-
-MSMD_EXPORT int msmd_rulebook_conv3d_fill(const int32_t* indices, int n, int batch_size,
-                                          const int* out_shape, const int* ksize,
-                                          const int* stride, const int* padding, int n_out,
-                                          int32_t* out_indices, int32_t* nbr_fwd,
-                                          int32_t* nbr_bwd, void* workspace,
-                                          size_t workspace_bytes, msmd_stream_t stream) {
-  Geom g;
-  if (!stride || !padding) return MSMD_ERR_INVALID_ARG;
-  int rc = check_geom(out_shape, ksize, stride, padding, batch_size, &g);
-  if (rc) return rc;
-  if (n < 0 || n_out < 0 || (n_out > 0 && (!out_indices || !nbr_fwd)))
-    return MSMD_ERR_INVALID_ARG;
-  Arena a(workspace, workspace_bytes);
-  ConvWs w;
-  carve_conv(a, &w, batch_size, out_shape);
-  if (!a.ok()) return MSMD_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  if (n_out > 0) hipMemsetAsync(nbr_fwd, 0xFF, sizeof(int32_t) * (size_t)g.kvol * n_out, st);
-  if (n > 0)
-    MSMD_LAUNCH(conv_fill<false>, dim3(ceil_div(n, 256), g.kvol), dim3(256), 0, st, indices, n, g,
-                       w.bits, w.prefix, n_out, out_indices, nbr_fwd, nbr_bwd);
-  return launch_status();
-}
-
-// ------------------------------------------------------------- transposed ---
-// getIndicePairsDeConv (geometry.h:196-245) on the strided builder's bitmap + rank scheme: the
-// output grid is the deconv size, (in - 1) * s - 2p + k + output_padding (ops.py:33-43), which
-// the caller passes as out_shape; the workspace is msmd_rulebook_conv_workspace_bytes of it.
-MSMD_EXPORT int msmd_rulebook_deconv3d_count(const int32_t* indices, int n, int batch_size,
-                                             const int* out_shape, const int* ksize,
-                                             const int* stride, const int* padding,
-                                             int32_t* n_out, void* workspace,
-                                             size_t workspace_bytes, msmd_stream_t stream) {
-  Geom g;
-  if (!stride || !padding || !n_out) return MSMD_ERR_INVALID_ARG;
-  int rc = check_geom(out_shape, ksize, stride, padding, batch_size, &g);
-  if (rc) return rc;
-  if (n < 0 || (n > 0 && !indices)) return MSMD_ERR_INVALID_ARG;
-  Arena a(workspace, workspace_bytes);
-  ConvWs w;
-  carve_conv(a, &w, batch_size, out_shape);
-  if (!a.ok()) return MSMD_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  hipMemsetAsync(w.bits, 0, sizeof(uint32_t) * w.words, st);
-  if (n > 0)
-    MSMD_LAUNCH(conv_mark<true>, dim3(ceil_div(n, 256), g.kvol), dim3(256), 0, st, indices, n, g,
-                w.bits);
-  device_scan(PopcCount{w.bits}, StorePrefix{w.prefix}, (int)w.words, w.tiles, n_out, -1, st);
-  return launch_status();
-}
-
-MSMD_EXPORT int msmd_rulebook_deconv3d_fill(const int32_t* indices, int n, int batch_size,
-                                            const int* out_shape, const int* ksize,
-                                            const int* stride, const int* padding, int n_out,
-                                            int32_t* out_indices, int32_t* nbr_fwd,
-                                            int32_t* nbr_bwd, void* workspace,
-                                            size_t workspace_bytes, msmd_stream_t stream) {
-  Geom g;
-  if (!stride || !padding) return MSMD_ERR_INVALID_ARG;
-  int rc = check_geom(out_shape, ksize, stride, padding, batch_size, &g);
-  if (rc) return rc;
-  if (n < 0 || n_out < 0 || (n_out > 0 && (!out_indices || !nbr_fwd)))
-    return MSMD_ERR_INVALID_ARG;
-  Arena a(workspace, workspace_bytes);
-  ConvWs w;
-  carve_conv(a, &w, batch_size, out_shape);
-  if (!a.ok()) return MSMD_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  if (n_out > 0) hipMemsetAsync(nbr_fwd, 0xFF, sizeof(int32_t) * (size_t)g.kvol * n_out, st);
-  if (n > 0)
-    MSMD_LAUNCH(conv_fill<true>, dim3(ceil_div(n, 256), g.kvol), dim3(256), 0, st, indices, n, g,
-                w.bits, w.prefix, n_out, out_indices, nbr_fwd, nbr_bwd);
   return launch_status();
 }
 
@@ -1161,22 +1132,9 @@ MSMD_EXPORT int msmd_rulebook_deconv3d_fill(const int32_t* indices, int n, int b
 // ONCE (7 dependent host reads per LC step before: each waited for its counting kernels'
 // turn next to the feature pass).  The fills run after the read through the existing entry
 // points (msmd_sparse_add_fill, msmd_rulebook_conv3d_fill) on this call's per-level
-// workspace regions, whose layouts are theirs: level l >= 1 has a union region (grid
-// in_shapes[l]) followed by its conv region (grid out_shapes[l]), level 0 (whose input set is
-// extra[0] as given) a conv region only; in_shapes[l] == out_shapes[l - 1].
-namespace {
-__global__ __launch_bounds__(256) void rows_mark(const int32_t* __restrict__ idx, int n, Geom g,
-                                                 uint32_t* bits) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int4 r = ((const int4*)idx)[i];
-  bitmap_set(bits, cell_id(r.x, r.y, r.z, r.w, g.shape));
-}
-inline size_t region_bytes(int batch, const int* shape) {
-  return align_up(msmd_rulebook_conv_workspace_bytes(batch, shape));
-}
-}  // namespace
-
+// workspace regions, each one voxel set's (voxel_set.hpp): level l >= 1 has a union region
+// (grid in_shapes[l]) followed by its conv region (grid out_shapes[l]), level 0 (whose input
+// set is extra[0] as given) a conv region only; in_shapes[l] == out_shapes[l - 1].
 MSMD_EXPORT size_t msmd_rulebook_add_conv_chain_workspace_bytes(int batch_size, int levels,
                                                                 const int* in_shapes,
                                                                 const int* out_shapes) {
@@ -1202,64 +1160,43 @@ MSMD_EXPORT int msmd_rulebook_add_conv_count_chain(const int32_t* const* extra, 
                                                                      out_shapes) ||
       ((uintptr_t)workspace & 255))
     return MSMD_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)workspace;
-  ConvWs prev{};
+  Geom g;         // conv geometry over the OUTPUT grid; gi: the input grid (union bitmap)
+  Shape3 gi;
+  // Every level is checked, in level order, before the first launch: a refused chain leaves
+  // nothing enqueued (msmd_rulebook_conv3d_count_chain checks a level right before its launches).
   for (int l = 0; l < levels; ++l) {
     if (n_extra[l] < 0 || (n_extra[l] > 0 && !extra[l])) return MSMD_ERR_INVALID_ARG;
-    Geom g;      // conv geometry over the OUTPUT grid; gi: the input grid (union bitmap)
     int rc = check_geom(out_shapes + 3 * l, ksizes + 3 * l, strides + 3 * l, paddings + 3 * l,
                         batch_size, &g);
+    if (!rc) rc = check_grid(batch_size, in_shapes + 3 * l, gi.s);
     if (rc) return rc;
-    const int* ish = in_shapes + 3 * l;
-    Geom gi = g;
-    double cells = batch_size;
-    for (int i = 0; i < 3; ++i) {
-      if (ish[i] < 1) return MSMD_ERR_INVALID_ARG;
-      gi.shape[i] = ish[i];
-      cells *= ish[i];
-    }
-    if (cells >= 4294967295.0) return MSMD_ERR_RANGE;
-    if (l > 0)
-      for (int i = 0; i < 3; ++i)
-        if (ish[i] != out_shapes[3 * (l - 1) + i]) return MSMD_ERR_INVALID_ARG;
-    // union region (levels >= 1)
-    const size_t ub = l ? region_bytes(batch_size, ish) : 0;
-    ConvWs u{};
+    for (int i = 0; l > 0 && i < 3; ++i)
+      if (in_shapes[3 * l + i] != out_shapes[3 * (l - 1) + i]) return MSMD_ERR_INVALID_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  char* base = (char*)workspace;
+  SetWs prev{};
+  for (int l = 0; l < levels; ++l) {
+    const int *ish = in_shapes + 3 * l, *osh = out_shapes + 3 * l;
+    // (validated above: these two calls only fill g and gi for this level)
+    check_geom(osh, ksizes + 3 * l, strides + 3 * l, paddings + 3 * l, batch_size, &g);
+    check_grid(batch_size, ish, gi.s);
+    // union region (levels >= 1): the previous output set and the level's own rows
+    SetWs u{};
     if (l > 0) {
-      Arena ua(base, ub);
-      carve_conv(ua, &u, batch_size, ish);
-      if (!ua.ok()) return MSMD_ERR_WORKSPACE;
+      const size_t ub = region_bytes(batch_size, ish);
+      if (!carve_set_at(base, ub, &u, batch_size, ish)) return MSMD_ERR_WORKSPACE;
       hipMemcpyAsync(u.bits, prev.bits, sizeof(uint32_t) * u.words, hipMemcpyDeviceToDevice, st);
-      if (n_extra[l] > 0)
-        MSMD_LAUNCH(rows_mark, dim3(ceil_div(n_extra[l], 256)), dim3(256), 0, st, extra[l],
-                    n_extra[l], gi, u.bits);
-      device_scan(PopcCount{u.bits}, StorePrefix{u.prefix}, (int)u.words, u.tiles, counts + 2 * l,
-                  -1, st);
+      mark_rows(extra[l], n_extra[l], gi, u.bits, st);
+      scan_set(u, counts + 2 * l, st);
+      base += ub;
     }
-    base += ub;
     // conv region
-    const size_t cb = region_bytes(batch_size, out_shapes + 3 * l);
-    Arena ca(base, cb);
-    ConvWs w;
-    carve_conv(ca, &w, batch_size, out_shapes + 3 * l);
-    if (!ca.ok()) return MSMD_ERR_WORKSPACE;
-    hipMemsetAsync(w.bits, 0, sizeof(uint32_t) * w.words, st);
-    if (l == 0) {
-      if (n_extra[0] > 0)
-        MSMD_LAUNCH(conv_mark<false>, dim3(ceil_div(n_extra[0], 256), g.kvol), dim3(256), 0, st, extra[0],
-                    n_extra[0], g, w.bits);
-    } else {
-      const long oc = (long)batch_size * g.shape[0] * g.shape[1] * g.shape[2];
-      if (oc <= kConvGatherCells)
-        MSMD_LAUNCH(conv_mark_gather, dim3(ceil_div(oc, 256)), dim3(256), 0, st,
-                    (const uint32_t*)u.bits, ish[0], ish[1], ish[2], g, oc, w.bits);
-      else
-        MSMD_LAUNCH(conv_mark_from_bits, dim3(ceil_div((long)u.words, 256)), dim3(256), 0, st,
-                    (const uint32_t*)u.bits, (long)u.words, ish[0], ish[1], ish[2], g, w.bits);
-    }
-    device_scan(PopcCount{w.bits}, StorePrefix{w.prefix}, (int)w.words, w.tiles,
-                counts + 2 * l + 1, -1, st);
+    const size_t cb = region_bytes(batch_size, osh);
+    SetWs w;
+    if (!carve_set_at(base, cb, &w, batch_size, osh)) return MSMD_ERR_WORKSPACE;
+    count_level<false>(extra[0], n_extra[0], l ? &u : nullptr, ish, batch_size, g, w,
+                       counts + 2 * l + 1, st);
     prev = w;
     base += cb;
   }

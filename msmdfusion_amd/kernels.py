@@ -653,6 +653,54 @@ def rulebook_subm(indices, batch_size, spatial_shape, ksize, method=None):
     return nbr
 
 
+_INT3 = C.c_int * 3
+
+
+class _StridedGeometry:
+    """[(ksize, stride, padding), ...] expanded against a grid, level l over level l - 1's
+    output grid: per level ks, st, pd, in_shape, out_shape, and the same as the flat c_int arrays
+    (f_ks, f_st, f_pd, f_in, f_out) the chain entry points take."""
+
+    def __init__(self, in_shape, geoms, out_size=conv_output_size):
+        self.ks, self.st, self.pd, self.in_shape, self.out_shape = [], [], [], [], []
+        shape = [int(v) for v in in_shape]
+        for ksize, stride, padding in geoms:
+            ks, st, pd = _expand3(ksize), _expand3(stride), _expand3(padding)
+            self.in_shape.append(list(shape))
+            shape = out_size(shape, ks, st, pd)
+            self.out_shape.append(list(shape))
+            self.ks.append(ks)
+            self.st.append(st)
+            self.pd.append(pd)
+        flat = lambda rows: (C.c_int * (3 * len(rows)))(*[v for r in rows for v in r])  # noqa: E731
+        self.f_ks, self.f_st, self.f_pd = flat(self.ks), flat(self.st), flat(self.pd)
+        self.f_in, self.f_out = flat(self.in_shape), flat(self.out_shape)
+
+    def level(self, l):
+        """(out_shape, ks, st, pd) of level l as the library takes one level's: its three ints
+        of the flat arrays, in place."""
+        return tuple(_INT3.from_buffer(f, 12 * l)
+                     for f in (self.f_out, self.f_ks, self.f_st, self.f_pd))
+
+
+def _region_bytes(batch_size, shape):
+    """The 256-byte-aligned workspace region of one voxel set on the grid `shape`: what the
+    chain entry points lay out per level, and what a fill of that level is handed."""
+    return (lib.msmd_rulebook_conv_workspace_bytes(int(batch_size), int3(shape)) + 255) // 256 * 256
+
+
+def _strided_fill(fill, idx, batch_size, geo, l, m, need_bwd, ws_addr, ws_bytes):
+    """Level l of geo over the rows idx, whose output set (m rows) has been counted into the
+    workspace at ws_addr -> (out_indices[m,4], nbr_fwd[K,m], nbr_bwd[K,n] | None)."""
+    n, dev, kvol = idx.shape[0], idx.device, kernel_volume(geo.ks[l])
+    out_idx = torch.empty((m, 4), dtype=torch.int32, device=dev)
+    nbr_fwd = torch.empty((kvol, m), dtype=torch.int32, device=dev)
+    nbr_bwd = torch.empty((kvol, n), dtype=torch.int32, device=dev) if need_bwd else None
+    check(fill(_p(idx), n, int(batch_size), *geo.level(l), m, _p(out_idx), _p(nbr_fwd),
+               _p(nbr_bwd), ws_addr, ws_bytes, _stream()), fill.__name__)
+    return out_idx, nbr_fwd, nbr_bwd
+
+
 def add_conv_chain(extras, batch_size, in_shape, geoms, need_bwd=True):
     """The fusion stack's stage chain with ONE host read: level l's strided conv (geoms[l] =
     (ksize, stride, padding)) runs over total_l = extras[0] for l = 0 and
@@ -671,60 +719,36 @@ def add_conv_chain(extras, batch_size, in_shape, geoms, need_bwd=True):
         _need_cuda(e)
         idx.append(e if (e.dtype == torch.int32 and e.is_contiguous()) else e.contiguous().int())
     dev = idx[0].device
-    ks = [_expand3(g[0]) for g in geoms]
-    st = [_expand3(g[1]) for g in geoms]
-    pd = [_expand3(g[2]) for g in geoms]
-    in_shapes, out_shapes, shape = [], [], list(in_shape)
-    for l in range(levels):
-        in_shapes.append(list(shape))
-        shape = conv_output_size(shape, ks[l], st[l], pd[l])
-        out_shapes.append(list(shape))
-    flat = lambda rows: (C.c_int * (3 * levels))(*[int(v) for r in rows for v in r])  # noqa: E731
-    f_in, f_out, f_ks, f_st, f_pd = flat(in_shapes), flat(out_shapes), flat(ks), flat(st), flat(pd)
-    nbytes = lib.msmd_rulebook_add_conv_chain_workspace_bytes(int(batch_size), levels, f_in, f_out)
+    geo = _StridedGeometry(in_shape, geoms)
+    nbytes = lib.msmd_rulebook_add_conv_chain_workspace_bytes(int(batch_size), levels, geo.f_in,
+                                                              geo.f_out)
     # (not the per-stream scratch: the fills below run after other library calls may have
     # used that one)
     ws = torch.empty((max(int(nbytes), 256),), dtype=torch.uint8, device=dev)
     ptrs = (C.c_void_p * levels)(*[t.data_ptr() for t in idx])
     ns = (C.c_int * levels)(*[int(t.shape[0]) for t in idx])
     counts = torch.empty((2 * levels,), dtype=torch.int32, device=dev)
-    check(lib.msmd_rulebook_add_conv_count_chain(ptrs, ns, int(batch_size), levels, f_in, f_out,
-                                                 f_ks, f_st, f_pd, _p(counts), _p(ws), nbytes,
-                                                 _stream()), "msmd_rulebook_add_conv_count_chain")
+    check(lib.msmd_rulebook_add_conv_count_chain(ptrs, ns, int(batch_size), levels, geo.f_in,
+                                                 geo.f_out, geo.f_ks, geo.f_st, geo.f_pd,
+                                                 _p(counts), _p(ws), nbytes, _stream()),
+          "msmd_rulebook_add_conv_count_chain")
     ms = counts.tolist()                                    # the chain's one host read
-    out, off, base, prev = [], 0, ws.data_ptr(), None
+    out, at, prev = [], ws.data_ptr(), None
     for l in range(levels):
-        ub = 0 if l == 0 else \
-            (lib.msmd_rulebook_conv_workspace_bytes(int(batch_size), int3(in_shapes[l])) + 255) \
-            // 256 * 256
-        cb = (lib.msmd_rulebook_conv_workspace_bytes(int(batch_size), int3(out_shapes[l])) + 255) \
-            // 256 * 256
-        kvol = kernel_volume(ks[l])
-        ma = mb = None
-        if l == 0:
-            total = idx[0]
-        else:
-            na, nb, m_u = idx[l].shape[0], prev.shape[0], int(ms[2 * l])
-            total = torch.empty((m_u, 4), dtype=torch.int32, device=dev)
-            ma = torch.empty((na,), dtype=torch.int32, device=dev)
-            mb = torch.empty((nb,), dtype=torch.int32, device=dev)
-            check(lib.msmd_sparse_add_fill(None, _p(idx[l]), na, None, _p(prev), nb, 0,
-                                           int(batch_size), int3(in_shapes[l]), m_u, _p(total),
-                                           None, _p(ma), _p(mb), base + off, ub, _stream()),
-                  "msmd_sparse_add_fill")
-        n, m = total.shape[0], int(ms[2 * l + 1])
-        out_idx = torch.empty((m, 4), dtype=torch.int32, device=dev)
-        nbr_fwd = torch.empty((kvol, m), dtype=torch.int32, device=dev)
-        nbr_bwd = torch.empty((kvol, n), dtype=torch.int32, device=dev) if need_bwd else None
-        check(lib.msmd_rulebook_conv3d_fill(_p(total), n, int(batch_size), int3(out_shapes[l]),
-                                            int3(ks[l]), int3(st[l]), int3(pd[l]), m, _p(out_idx),
-                                            _p(nbr_fwd), _p(nbr_bwd), base + off + ub, cb,
-                                            _stream()), "msmd_rulebook_conv3d_fill")
+        total, ma, mb = idx[0], None, None
+        if l > 0:                        # the union region, then the level's conv region
+            ub = _region_bytes(batch_size, geo.in_shape[l])
+            total, _, ma, mb = _sparse_add_fill(None, idx[l], None, prev, batch_size,
+                                                geo.in_shape[l], int(ms[2 * l]), at, ub)
+            at += ub
+        cb = _region_bytes(batch_size, geo.out_shape[l])
+        out_idx, nbr_fwd, nbr_bwd = _strided_fill(lib.msmd_rulebook_conv3d_fill, total, batch_size,
+                                                  geo, l, int(ms[2 * l + 1]), need_bwd, at, cb)
+        at += cb
         out.append(dict(total_indices=total, map_a=ma, map_b=mb, out_indices=out_idx,
-                        nbr_fwd=nbr_fwd, nbr_bwd=nbr_bwd, in_shape=in_shapes[l],
-                        out_shape=out_shapes[l]))
+                        nbr_fwd=nbr_fwd, nbr_bwd=nbr_bwd, in_shape=geo.in_shape[l],
+                        out_shape=geo.out_shape[l]))
         prev = out_idx
-        off += ub + cb
     return out
 
 
@@ -774,31 +798,27 @@ def rulebook_subm_many(jobs):
           "msmd_rulebook_subm3d_many")
 
 
-def rulebook_conv(indices, batch_size, spatial_shape, ksize, stride, padding, need_bwd=True):
-    """-> (out_indices[M,4], nbr_fwd[K,M], nbr_bwd[K,N] | None, out_shape)"""
+def _rulebook_strided(indices, batch_size, spatial_shape, geom, out_size, count, fill, need_bwd):
+    """One strided or transposed level (geom = (ksize, stride, padding), out_size its output
+    grid): count the output set, read the count, fill."""
     _need_bzyx(indices)
     _need_cuda(indices)
     idx = indices.contiguous().int()
-    n = idx.shape[0]
-    dev = idx.device
-    ks, st, pd = _expand3(ksize), _expand3(stride), _expand3(padding)
-    out_shape = conv_output_size(list(spatial_shape), ks, st, pd)
-    kvol = kernel_volume(ks)
-    nbytes = lib.msmd_rulebook_conv_workspace_bytes(int(batch_size), int3(out_shape))
-    ws = _ws(nbytes, dev)
-    count = _Count(dev)
-    check(lib.msmd_rulebook_conv3d_count(_p(idx), n, int(batch_size), int3(out_shape), int3(ks),
-                                         int3(st), int3(pd), count.ptr, _p(ws), nbytes, _stream()),
-          "msmd_rulebook_conv3d_count")
-    m = count.read()
-    out_idx = torch.empty((m, 4), dtype=torch.int32, device=dev)
-    nbr_fwd = torch.empty((kvol, m), dtype=torch.int32, device=dev)
-    nbr_bwd = torch.empty((kvol, n), dtype=torch.int32, device=dev) if need_bwd else None
-    check(lib.msmd_rulebook_conv3d_fill(_p(idx), n, int(batch_size), int3(out_shape), int3(ks),
-                                        int3(st), int3(pd), m, _p(out_idx), _p(nbr_fwd),
-                                        _p(nbr_bwd), _p(ws), nbytes, _stream()),
-          "msmd_rulebook_conv3d_fill")
-    return out_idx, nbr_fwd, nbr_bwd, out_shape
+    geo = _StridedGeometry(spatial_shape, [geom], out_size)
+    nbytes = lib.msmd_rulebook_conv_workspace_bytes(int(batch_size), geo.f_out)
+    ws = _ws(nbytes, idx.device)
+    m = _Count(idx.device)
+    check(count(_p(idx), idx.shape[0], int(batch_size), geo.f_out, geo.f_ks, geo.f_st, geo.f_pd,
+                m.ptr, _p(ws), nbytes, _stream()), count.__name__)
+    return _strided_fill(fill, idx, batch_size, geo, 0, m.read(), need_bwd, _p(ws), nbytes) \
+        + (geo.out_shape[0],)
+
+
+def rulebook_conv(indices, batch_size, spatial_shape, ksize, stride, padding, need_bwd=True):
+    """-> (out_indices[M,4], nbr_fwd[K,M], nbr_bwd[K,N] | None, out_shape)"""
+    return _rulebook_strided(indices, batch_size, spatial_shape, (ksize, stride, padding),
+                             conv_output_size, lib.msmd_rulebook_conv3d_count,
+                             lib.msmd_rulebook_conv3d_fill, need_bwd)
 
 
 def rulebook_conv_chain(indices, batch_size, spatial_shape, geoms, need_bwd=True):
@@ -811,37 +831,23 @@ def rulebook_conv_chain(indices, batch_size, spatial_shape, geoms, need_bwd=True
     idx = indices.contiguous().int()
     dev = idx.device
     levels = len(geoms)
-    ks = [_expand3(g[0]) for g in geoms]
-    st = [_expand3(g[1]) for g in geoms]
-    pd = [_expand3(g[2]) for g in geoms]
-    shapes, shape = [], list(spatial_shape)
-    for l in range(levels):
-        shape = conv_output_size(shape, ks[l], st[l], pd[l])
-        shapes.append(list(shape))
-    flat = lambda rows: (C.c_int * (3 * levels))(*[int(v) for r in rows for v in r])  # noqa: E731
-    f_shapes, f_ks, f_st, f_pd = flat(shapes), flat(ks), flat(st), flat(pd)
-    nbytes = lib.msmd_rulebook_conv_chain_workspace_bytes(int(batch_size), levels, f_shapes)
+    geo = _StridedGeometry(spatial_shape, geoms)
+    nbytes = lib.msmd_rulebook_conv_chain_workspace_bytes(int(batch_size), levels, geo.f_out)
     ws = _ws(nbytes, dev)
     counts = torch.empty((levels,), dtype=torch.int32, device=dev)
     check(lib.msmd_rulebook_conv3d_count_chain(_p(idx), idx.shape[0], int(batch_size), levels,
-                                               f_shapes, f_ks, f_st, f_pd, _p(counts), _p(ws),
-                                               nbytes, _stream()),
+                                               geo.f_out, geo.f_ks, geo.f_st, geo.f_pd, _p(counts),
+                                               _p(ws), nbytes, _stream()),
           "msmd_rulebook_conv3d_count_chain")
     ms = counts.tolist()                                    # the chain's one host read
-    out, off, base = [], 0, ws.data_ptr()
+    out, at = [], ws.data_ptr()
     for l in range(levels):
-        n, m, kvol = idx.shape[0], int(ms[l]), kernel_volume(ks[l])
-        lvl_bytes = lib.msmd_rulebook_conv_workspace_bytes(int(batch_size), int3(shapes[l]))
-        out_idx = torch.empty((m, 4), dtype=torch.int32, device=dev)
-        nbr_fwd = torch.empty((kvol, m), dtype=torch.int32, device=dev)
-        nbr_bwd = torch.empty((kvol, n), dtype=torch.int32, device=dev) if need_bwd else None
-        check(lib.msmd_rulebook_conv3d_fill(_p(idx), n, int(batch_size), int3(shapes[l]),
-                                            int3(ks[l]), int3(st[l]), int3(pd[l]), m, _p(out_idx),
-                                            _p(nbr_fwd), _p(nbr_bwd), C.c_void_p(base + off),
-                                            lvl_bytes, _stream()), "msmd_rulebook_conv3d_fill")
-        out.append((out_idx, nbr_fwd, nbr_bwd, shapes[l]))
-        off += (lvl_bytes + 255) // 256 * 256
-        idx = out_idx
+        lvl_bytes = _region_bytes(batch_size, geo.out_shape[l])
+        tables = _strided_fill(lib.msmd_rulebook_conv3d_fill, idx, batch_size, geo, l, int(ms[l]),
+                               need_bwd, at, lvl_bytes)
+        out.append(tables + (geo.out_shape[l],))
+        at += lvl_bytes
+        idx = tables[0]
     return out
 
 
@@ -861,31 +867,14 @@ def rulebook_deconv(indices, batch_size, spatial_shape, ksize, stride, padding,
     """Transposed-conv rulebook (geometry.h:196-245): input c reaches c*s - p + k.
     -> (out_indices[M,4] in ascending linear id, nbr_fwd[K,M], nbr_bwd[K,N] | None, out_shape);
     one host read (the output count)."""
-    _need_bzyx(indices)
-    _need_cuda(indices)
-    idx = indices.contiguous().int()
-    n = idx.shape[0]
-    dev = idx.device
-    ks, st, pd = _expand3(ksize), _expand3(stride), _expand3(padding)
-    out_shape = deconv_output_size(list(spatial_shape), ks, st, pd, output_padding)
-    if any(s < 1 for s in out_shape):
-        raise ValueError("transposed conv output shape %s is empty" % (out_shape,))
-    kvol = kernel_volume(ks)
-    nbytes = lib.msmd_rulebook_conv_workspace_bytes(int(batch_size), int3(out_shape))
-    ws = _ws(nbytes, dev)
-    count = _Count(dev)
-    check(lib.msmd_rulebook_deconv3d_count(_p(idx), n, int(batch_size), int3(out_shape),
-                                           int3(ks), int3(st), int3(pd), count.ptr, _p(ws),
-                                           nbytes, _stream()), "msmd_rulebook_deconv3d_count")
-    m = count.read()
-    out_idx = torch.empty((m, 4), dtype=torch.int32, device=dev)
-    nbr_fwd = torch.empty((kvol, m), dtype=torch.int32, device=dev)
-    nbr_bwd = torch.empty((kvol, n), dtype=torch.int32, device=dev) if need_bwd else None
-    check(lib.msmd_rulebook_deconv3d_fill(_p(idx), n, int(batch_size), int3(out_shape), int3(ks),
-                                          int3(st), int3(pd), m, _p(out_idx), _p(nbr_fwd),
-                                          _p(nbr_bwd), _p(ws), nbytes, _stream()),
-          "msmd_rulebook_deconv3d_fill")
-    return out_idx, nbr_fwd, nbr_bwd, out_shape
+    def out_size(*geom):
+        out_shape = deconv_output_size(*geom, output_padding)
+        if any(s < 1 for s in out_shape):
+            raise ValueError("transposed conv output shape %s is empty" % (out_shape,))
+        return out_shape
+    return _rulebook_strided(indices, batch_size, spatial_shape, (ksize, stride, padding), out_size,
+                             lib.msmd_rulebook_deconv3d_count, lib.msmd_rulebook_deconv3d_fill,
+                             need_bwd)
 
 
 def rulebook_pairs(nbr, ld=None):
@@ -1969,49 +1958,43 @@ def sigmoid_focal(logits, labels, weights, gamma=2.0, alpha=0.25, want_grad=True
     return total, grad
 
 
-def sparse_add(feat_a, idx_a, feat_b, idx_b, batch_size, spatial_shape):
-    """-> (out_indices, out_feat, map_a, map_b)"""
-    _need_bzyx(idx_a, idx_b)
-    _need_cuda(feat_a, idx_a, feat_b, idx_b)
-    fa, fb = feat_a.contiguous().float(), feat_b.contiguous().float()
-    ia, ib = idx_a.contiguous().int(), idx_b.contiguous().int()
-    na, nb, c = fa.shape[0], fb.shape[0], fa.shape[1]
-    dev = fa.device
-    nbytes = lib.msmd_sparse_add_workspace_bytes(int(batch_size), int3(spatial_shape))
-    ws = _ws(nbytes, dev)
-    count = _Count(dev)
-    check(lib.msmd_sparse_add_count(_p(ia), na, _p(ib), nb, int(batch_size), int3(spatial_shape),
-                                    count.ptr, _p(ws), nbytes, _stream()), "msmd_sparse_add_count")
-    m = count.read()
+def _sparse_add_fill(feat_a, idx_a, feat_b, idx_b, batch_size, spatial_shape, m, ws_addr,
+                     ws_bytes):
+    """The union set (m rows) counted into the workspace at ws_addr -> (out_indices, out_feat,
+    map_a, map_b) in ONE fill launch set; without features (None) the index half alone."""
+    na, nb, dev = idx_a.shape[0], idx_b.shape[0], idx_a.device
+    c = 0 if feat_a is None else feat_a.shape[1]
     oi = torch.empty((m, 4), dtype=torch.int32, device=dev)
-    of = torch.empty((m, c), dtype=torch.float32, device=dev)
+    of = None if feat_a is None else torch.empty((m, c), dtype=torch.float32, device=dev)
     ma = torch.empty((na,), dtype=torch.int32, device=dev)
     mb = torch.empty((nb,), dtype=torch.int32, device=dev)
-    check(lib.msmd_sparse_add_fill(_p(fa), _p(ia), na, _p(fb), _p(ib), nb, c, int(batch_size),
-                                   int3(spatial_shape), m, _p(oi), _p(of), _p(ma), _p(mb), _p(ws),
-                                   nbytes, _stream()), "msmd_sparse_add_fill")
+    check(lib.msmd_sparse_add_fill(_p(feat_a), _p(idx_a), na, _p(feat_b), _p(idx_b), nb, c,
+                                   int(batch_size), int3(spatial_shape), m, _p(oi), _p(of), _p(ma),
+                                   _p(mb), ws_addr, ws_bytes, _stream()), "msmd_sparse_add_fill")
     return oi, of, ma, mb
+
+
+def sparse_add(feat_a, idx_a, feat_b, idx_b, batch_size, spatial_shape):
+    """-> (out_indices, out_feat, map_a, map_b); without features (None, as sparse_add_index
+    calls it) the index half alone, out_feat = None."""
+    _need_bzyx(idx_a, idx_b)
+    _need_cuda(feat_a, idx_a, feat_b, idx_b)
+    if feat_a is not None:
+        feat_a, feat_b = feat_a.contiguous().float(), feat_b.contiguous().float()
+    ia, ib = idx_a.contiguous().int(), idx_b.contiguous().int()
+    nbytes = lib.msmd_sparse_add_workspace_bytes(int(batch_size), int3(spatial_shape))
+    ws = _ws(nbytes, ia.device)
+    count = _Count(ia.device)
+    check(lib.msmd_sparse_add_count(_p(ia), ia.shape[0], _p(ib), ib.shape[0], int(batch_size),
+                                    int3(spatial_shape), count.ptr, _p(ws), nbytes, _stream()),
+          "msmd_sparse_add_count")
+    return _sparse_add_fill(feat_a, ia, feat_b, ib, batch_size, spatial_shape, count.read(),
+                            _p(ws), nbytes)
 
 
 def sparse_add_index(idx_a, idx_b, batch_size, spatial_shape):
     """Index half of sparse_add -> (out_indices[m,4], map_a[na], map_b[nb])."""
-    _need_bzyx(idx_a, idx_b)
-    _need_cuda(idx_a, idx_b)
-    ia, ib = idx_a.contiguous().int(), idx_b.contiguous().int()
-    na, nb = ia.shape[0], ib.shape[0]
-    dev = ia.device
-    nbytes = lib.msmd_sparse_add_workspace_bytes(int(batch_size), int3(spatial_shape))
-    ws = _ws(nbytes, dev)
-    count = _Count(dev)
-    check(lib.msmd_sparse_add_count(_p(ia), na, _p(ib), nb, int(batch_size), int3(spatial_shape),
-                                    count.ptr, _p(ws), nbytes, _stream()), "msmd_sparse_add_count")
-    m = count.read()
-    oi = torch.empty((m, 4), dtype=torch.int32, device=dev)
-    ma = torch.empty((na,), dtype=torch.int32, device=dev)
-    mb = torch.empty((nb,), dtype=torch.int32, device=dev)
-    check(lib.msmd_sparse_add_fill(None, _p(ia), na, None, _p(ib), nb, 0, int(batch_size),
-                                   int3(spatial_shape), m, _p(oi), None, _p(ma), _p(mb), _p(ws),
-                                   nbytes, _stream()), "msmd_sparse_add_fill")
+    oi, _, ma, mb = sparse_add(None, idx_a, None, idx_b, batch_size, spatial_shape)
     return oi, ma, mb
 
 

@@ -41,17 +41,21 @@ def _tables(can, n_in, n_out):
     return fwd, bwd
 
 
-def _check_deconv(dev, idx, batch, ks, st, pd, op, shape=SHAPE):
+def _check_deconv(dev, idx, batch, ks, st, pd, op, shape=SHAPE, need_bwd=True):
     out_shape = R.deconv_output_size(shape, ks, st, pd, op)
     oi, pr, nm = R.deconv_pairs(idx, out_shape, ks, st, pd)
     coi, can, _ = O.canonical_rulebook(oi, pr, nm, out_shape)
     d_idx = torch.from_numpy(np.ascontiguousarray(idx, np.int32).reshape(-1, 4)).to(dev)
-    out_idx, nbr_fwd, nbr_bwd, got_shape = K.rulebook_deconv(d_idx, batch, shape, ks, st, pd, op)
+    out_idx, nbr_fwd, nbr_bwd, got_shape = K.rulebook_deconv(d_idx, batch, shape, ks, st, pd, op,
+                                                             need_bwd=need_bwd)
     assert list(got_shape) == out_shape
     assert np.array_equal(_np(out_idx), coi.reshape(-1, 4))
     fwd, bwd = _tables(can, idx.shape[0], coi.shape[0])
     assert np.array_equal(_np(nbr_fwd), fwd)
-    assert np.array_equal(_np(nbr_bwd), bwd)
+    if need_bwd:
+        assert np.array_equal(_np(nbr_bwd), bwd)
+    else:
+        assert nbr_bwd is None
     # reference-format pairs through the shim
     ids, pairs, num = ext.get_indice_pairs_3d(d_idx, batch, out_shape, shape, ks, st, pd,
                                               [1, 1, 1], op, 0, 1)
@@ -85,6 +89,12 @@ def test_transposed_rulebook_edges(dev):
     # every output outside the grid: k1 s1 p2 shrinks the grid by 2 on each side
     out = np.array([[0, 0, 0, 0], [0, 1, 1, 1], [0, 6, 11, 9], [0, 0, 5, 5]], np.int32)
     coi = _check_deconv(dev, out, 1, [1, 1, 1], [1, 1, 1], [2, 2, 2], [0, 0, 0])
+    assert coi.shape[0] == 0
+    # without the backward table: a filled and an empty input
+    small = [4, 6, 6]
+    some = R.random_voxels(np.random.RandomState(3), 2, small, 30)
+    assert _check_deconv(dev, some, 2, ks, st, pd, op, small, need_bwd=False).shape[0] > 0
+    coi = _check_deconv(dev, np.zeros((0, 4), np.int32), 2, ks, st, pd, op, small, need_bwd=False)
     assert coi.shape[0] == 0
 
 
