@@ -1333,6 +1333,90 @@ int msmd_sigmoid_focal_f32(const float* logits /* [n,num_classes] */,
                            float* grad /* [n,num_classes] or NULL */, float* sum /* [1] */,
                            void* workspace, size_t workspace_bytes, msmd_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * n4  VoteNet: matrix-free Chamfer distance, vote targets, points per box (csrc/vote.hip) and
+ *     the class-aware axis-aligned 3-D NMS (csrc/nms.hip)
+ * replaces: chamfer_distance  (mmdet3d/models/losses/chamfer_distance.py:50-55: two
+ *           [B, N, M, 3] expansions, a [B, N, M] matrix, two torch.min) and autograd through it
+ *           VoteHead.get_targets_single  (models/dense_heads/vote_head.py:472-501: a Python loop
+ *           over ground truths with a torch.nonzero per box and per slot)
+ *           VoteHead.multiclass_nms_single  (vote_head.py:617-625: an [N, T] inclusion table,
+ *           only summed over N)
+ *           aligned_3d_nms  (mmdet3d/core/post_processing/box3d_nms.py:91-138: a Python while
+ *           loop with one host read per kept box)
+ * Nothing here uses float atomics; every result is bitwise reproducible; nothing is read back.
+ * ------------------------------------------------------------------------ */
+/* Chamfer forward.  c(s, t) = (cx + cy) + cz in float32, every operation rounded on its own,
+ * with the per-coordinate criterion on d = s - t: mode 0 (l2) d * d, 1 (l1) |d|, 2 (smooth_l1,
+ * beta 1) (0.5 |d|) |d| for |d| < 1 else |d| - 0.5.
+ *   d1[b, n] = min over m of c(src[b, n], dst[b, m]), i1[b, n] = its index; d2 / i2 likewise
+ *   over n for every dst[b, m].
+ * The minimum is torch.min's over a dimension: ties go to the lowest index, a NaN distance is
+ * the minimum and the first NaN is reported.  channels != 3, n == 0 or m == 0 are refused
+ * (MSMD_ERR_INVALID_ARG).  No buffer of size N x M exists; no workspace. */
+int msmd_chamfer_fwd_f32(const float* src /* [batch,n,3] */, const float* dst /* [batch,m,3] */,
+                         int batch, int n, int m, int channels, int mode,
+                         float* d1 /* [batch,n] */, int64_t* i1 /* [batch,n] */,
+                         float* d2 /* [batch,m] */, int64_t* i2 /* [batch,m] */,
+                         msmd_stream_t stream);
+/* Chamfer backward for upstream g1 [batch, n] (of d1) and g2 [batch, m] (of d2), with
+ * c'(d) = 2 d (l2), sign(d) with sign(0) = 0 (l1), d for |d| < 1 else sign(d) (smooth_l1):
+ *   grad_src[b, n] = g1[b, n] c'(src_n - dst_{i1[n]}), then + g2[b, m] c'(src_n - dst_m) for
+ *   every m with i2[b, m] == n in ascending m;
+ *   grad_dst[b, m] = g2[b, m] c'(dst_m - src_{i2[m]}), then + g1[b, n] c'(dst_m - src_n) for
+ *   every n with i1[b, n] == m in ascending n.
+ * The differences are float32; the products and the running sum (a left fold in that order) are
+ * double, rounded to float32 once at the end.
+ * One lane per output point scans the other side's index array; no atomics, no sort.  An index
+ * outside its set contributes nothing.  Either gradient may be NULL (not computed). */
+int msmd_chamfer_bwd_f32(const float* src /* [batch,n,3] */, const float* dst /* [batch,m,3] */,
+                         const float* g1 /* [batch,n] */, const float* g2 /* [batch,m] */,
+                         const int64_t* i1 /* [batch,n] */, const int64_t* i2 /* [batch,m] */,
+                         int batch, int n, int m, int channels, int mode,
+                         float* grad_src /* [batch,n,3] or NULL */,
+                         float* grad_dst /* [batch,m,3] or NULL */, msmd_stream_t stream);
+/* Vote targets of the box form (bbox_coder.with_rot).  Sample s owns point rows
+ * point_offsets[s] .. point_offsets[s+1] and box rows box_offsets[s] .. box_offsets[s+1]; boxes
+ * are in the frame of msmd_points_in_boxes_f32 (x, y, z bottom, w, l, h, rz) and tested with
+ * its predicate; centers are their gravity centres.  With k = the boxes of the point's sample
+ * that hold it, in ascending box order, and vote(box) = center - point[:3]:
+ *   vote_mask = (k > 0); slot 0 = vote(first); slot 1 = vote(second) if k >= 2 else
+ *   vote(first); slot 2 = vote(LAST) if k >= 3 else vote(first) -- the reference clamps its
+ *   slot counter at 2, so every later box overwrites slot 2; all zero when k == 0.
+ * Every row of both outputs that the offsets cover is written.  gt_per_seed must be 3.
+ * max_points (a bound on a sample's points known to the host) only sizes the grid. */
+int msmd_vote_targets_f32(const float* points /* [total_points,ld] */, int ld,
+                          const int32_t* point_offsets /* [num_samples+1] */,
+                          const float* boxes /* [total_boxes,7] */,
+                          const float* centers /* [total_boxes,3] */,
+                          const int32_t* box_offsets /* [num_samples+1] */, int num_samples,
+                          int total_points, int total_boxes, int max_points, int gt_per_seed,
+                          float* vote_targets /* [total_points,9] */,
+                          int64_t* vote_mask /* [total_points] */, msmd_stream_t stream);
+/* count[b, t] = the points of sample b inside box t (the predicate of
+ * msmd_points_in_boxes_f32), summed in integers; no [M, T] table. */
+int msmd_points_in_boxes_count_f32(const float* boxes /* [B,T,7] */,
+                                   const float* pts /* [B,M,ld] */, int ld, int batch_size,
+                                   int num_boxes, int num_points, int32_t* count /* [B,T] */,
+                                   msmd_stream_t stream);
+/* Class-aware axis-aligned 3-D NMS over segments; rows (x1, y1, z1, x2, y2, z2, class) in
+ * descending score order.  offsets, max_segment, thresh, post_max, order, keep, keep_stride,
+ * num_keep and the workspace are those of msmd_nms_batched_f32.  A kept row i suppresses a
+ * later row j when !((iou * same) <= thresh[s]) with inter = the product of the three
+ * fmaxf(0, min(hi) - max(lo)) extents, iou = inter / (vol_i + vol_j - inter) and
+ * same = (class_i == class_j) ? 1 : 0, all float32 and rounded one operation at a time.  That
+ * is the reference's `score_sorted[iou <= thresh]` as written: a NaN IoU (0 / 0, two disjoint
+ * zero-volume boxes) suppresses, and across classes, because NaN * 0 is NaN. */
+size_t msmd_nms_aligned3d_workspace_bytes(int total_boxes, int max_segment);
+int msmd_nms_aligned3d_f32(const float* boxes /* [total_boxes, ld >= 7] */, int ld,
+                           const int32_t* offsets /* [num_segments + 1] */, int num_segments,
+                           int total_boxes, int max_segment,
+                           const float* thresh /* [num_segments] */, int post_max,
+                           const int64_t* order /* [total_boxes] or NULL */,
+                           int64_t* keep /* [num_segments, keep_stride] */, int keep_stride,
+                           int32_t* num_keep /* [num_segments] */, void* workspace,
+                           size_t workspace_bytes, msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -203,6 +203,13 @@ SIGNATURES = {
                                      _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "msmd_sigmoid_focal_workspace_bytes": (_sz, [_i64, _i]),
     "msmd_sigmoid_focal_f32": (_i, [_vp, _vp, _vp, _i64, _i, _f, _f, _vp, _vp, _vp, _sz, _vp]),
+    "msmd_chamfer_fwd_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "msmd_chamfer_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "msmd_vote_targets_f32": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "msmd_points_in_boxes_count_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "msmd_nms_aligned3d_workspace_bytes": (_sz, [_i, _i]),
+    "msmd_nms_aligned3d_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _sz,
+                                    _vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -319,6 +319,70 @@ SECOND_SECFPN_KITTI = dict(model=dict(
     train_cfg=_KITTI_SECOND_TRAIN, test_cfg=_KITTI_SECOND_TEST))
 
 
+# ---------------------------------------------------------------------------------------------
+# VoteNet (configs/_base_/models/votenet.py under configs/votenet/votenet_16x8_sunrgbd-3d-10class.py
+# and votenet_8x8_scannet-3d-18class.py): PointNet2SASSG + VoteHead.  SUN RGB-D boxes carry a
+# yaw (12 direction bins, box-form vote targets); ScanNet boxes are axis-aligned (one bin,
+# instance-mask vote targets).  tests/golden/reference_votenet_configs.json holds the reference's
+# values.
+_SUNRGBD_MEAN_SIZES = [
+    [2.114256, 1.620300, 0.927272], [0.791118, 1.279516, 0.718182], [0.923508, 1.867419, 0.845495],
+    [0.591958, 0.552978, 0.827272], [0.699104, 0.454178, 0.75625], [0.69519, 1.346299, 0.736364],
+    [0.528526, 1.002642, 1.172878], [0.500618, 0.632163, 0.683424], [0.404671, 1.071108, 1.688889],
+    [0.76584, 1.398258, 0.472728]]
+_SCANNET_MEAN_SIZES = [
+    [0.76966727, 0.8116021, 0.92573744], [1.876858, 1.8425595, 1.1931566],
+    [0.61328, 0.6148609, 0.7182701], [1.3955007, 1.5121545, 0.83443564],
+    [0.97949594, 1.0675149, 0.6329687], [0.531663, 0.5955577, 1.7500148],
+    [0.9624706, 0.72462326, 1.1481868], [0.83221924, 1.0490936, 1.6875663],
+    [0.21132214, 0.4206159, 0.5372846], [1.4440073, 1.8970833, 0.26985747],
+    [1.0294262, 1.4040797, 0.87554324], [1.3766412, 0.65521795, 1.6813129],
+    [0.6650819, 0.71111923, 1.298853], [0.41999173, 0.37906948, 1.7513971],
+    [0.59359556, 0.5912492, 0.73919016], [0.50867593, 0.50656086, 0.30136237],
+    [1.1511526, 1.0546296, 0.49706793], [0.47535285, 0.49249494, 0.5802117]]
+
+
+def _votenet(num_classes, num_dir_bins, with_rot, mean_sizes):
+    return dict(model=dict(
+        type="VoteNet",
+        backbone=dict(
+            type="PointNet2SASSG", in_channels=4, num_points=(2048, 1024, 512, 256),
+            radius=(0.2, 0.4, 0.8, 1.2), num_samples=(64, 32, 16, 16),
+            sa_channels=((64, 64, 128), (128, 128, 256), (128, 128, 256), (128, 128, 256)),
+            fp_channels=((256, 256), (256, 256)), norm_cfg=dict(type="BN2d"),
+            sa_cfg=dict(type="PointSAModule", pool_mod="max", use_xyz=True, normalize_xyz=True)),
+        bbox_head=dict(
+            type="VoteHead",
+            vote_module_cfg=dict(
+                in_channels=256, vote_per_seed=1, gt_per_seed=3, conv_channels=(256, 256),
+                conv_cfg=dict(type="Conv1d"), norm_cfg=dict(type="BN1d"), norm_feats=True,
+                vote_loss=dict(type="ChamferDistance", mode="l1", reduction="none",
+                               loss_dst_weight=10.0)),
+            vote_aggregation_cfg=dict(
+                type="PointSAModule", num_point=256, radius=0.3, num_sample=16,
+                mlp_channels=[256, 128, 128, 128], use_xyz=True, normalize_xyz=True),
+            pred_layer_cfg=dict(in_channels=128, shared_conv_channels=(128, 128), bias=True),
+            conv_cfg=dict(type="Conv1d"), norm_cfg=dict(type="BN1d"),
+            objectness_loss=dict(type="CrossEntropyLoss", class_weight=[0.2, 0.8],
+                                 reduction="sum", loss_weight=5.0),
+            center_loss=dict(type="ChamferDistance", mode="l2", reduction="sum",
+                             loss_src_weight=10.0, loss_dst_weight=10.0),
+            dir_class_loss=dict(type="CrossEntropyLoss", reduction="sum", loss_weight=1.0),
+            dir_res_loss=dict(type="SmoothL1Loss", reduction="sum", loss_weight=10.0),
+            size_class_loss=dict(type="CrossEntropyLoss", reduction="sum", loss_weight=1.0),
+            size_res_loss=dict(type="SmoothL1Loss", reduction="sum", loss_weight=10.0 / 3.0),
+            semantic_loss=dict(type="CrossEntropyLoss", reduction="sum", loss_weight=1.0),
+            num_classes=num_classes,
+            bbox_coder=dict(type="PartialBinBasedBBoxCoder", num_sizes=num_classes,
+                            num_dir_bins=num_dir_bins, with_rot=with_rot, mean_sizes=mean_sizes)),
+        train_cfg=dict(pos_distance_thr=0.3, neg_distance_thr=0.6, sample_mod="vote"),
+        test_cfg=dict(sample_mod="seed", nms_thr=0.25, score_thr=0.05, per_class_proposal=True)))
+
+
+VOTENET_SUNRGBD = _votenet(10, 12, True, _SUNRGBD_MEAN_SIZES)
+VOTENET_SCANNET = _votenet(18, 1, False, _SCANNET_MEAN_SIZES)
+
+
 def build_hot_path(cfg):
     """(Voxelization, voxel encoder, SparseEncoder, multimodal encoder | None) from one of
     the dicts above -- what MSMDFusionDetector.__init__ / MVXTwoStageDetector.__init__ build

@@ -1,5 +1,6 @@
 // nms.hip -- the iou3d op family's suppression side (COVERAGE n2): rotated, axis-aligned and
-// circle NMS, batched over segments, with the greedy reduction on the device.
+// circle NMS, batched over segments, with the greedy reduction on the device; and the
+// class-aware axis-aligned 3-D NMS of the VoteNet family (COVERAGE n4) on the same two kernels.
 //
 //   nms_mask_kernel    ops/iou3d/src/iou3d_kernel.cu nms_kernel / nms_normal_kernel (:283-419)
 //                      and the pair test of core/post_processing/box3d_nms.py:158-181
@@ -9,6 +10,8 @@
 //                      device-side: one wavefront per segment walks the rows 64 at a time with
 //                      the "removed" bitset in LDS.
 //   boxes_iou_bev      iou3d_kernel.cu boxes_iou_bev_kernel (:269-281).
+//   hit_aligned3d      the pair test of core/post_processing/box3d_nms.py:91-138
+//                      (aligned_3d_nms, a Python while loop with one host read per kept box).
 //
 // A segment is one (task, sample) list of boxes, sorted by descending score by the caller and
 // addressed through a CSR offsets array that stays on the device.  The host only knows an
@@ -27,7 +30,7 @@ constexpr int kNmsTile = 64;                 // rows / columns per tile = bits p
 constexpr int kNmsMaxSegment = 16384;        // removed bitset: 256 words = 2 KB of LDS
 constexpr int kNmsMaxWords = kNmsMaxSegment / kNmsTile;
 
-enum { kRotated = 0, kNormal = 1, kCircle = 2 };
+enum { kRotated = 0, kNormal = 1, kCircle = 2, kAligned3d = 3 };
 
 // iou3d_kernel.cu:244-251
 __device__ __forceinline__ float iou_bev(const Box& a, const Box& b) {
@@ -56,6 +59,24 @@ __device__ __forceinline__ bool circle_hit(const float* kept, const float* later
   return dist <= thresh;
 }
 
+// box3d_nms.py:119-135 on rows (x1, y1, z1, x2, y2, z2, class): the kept row suppresses the later
+// one unless iou * same <= thresh, as the reference's `score_sorted[iou <= thresh]` keeps it.
+// A NaN IoU (0 / 0: two zero-volume boxes that do not intersect) therefore suppresses, and in
+// any class, because NaN * 0 is NaN.  Every product, sum and the quotient rounded on its own.
+__device__ __forceinline__ float volume3d(const float* b) {
+  return __fmul_rn(__fmul_rn(__fsub_rn(b[3], b[0]), __fsub_rn(b[4], b[1])), __fsub_rn(b[5], b[2]));
+}
+__device__ __forceinline__ bool hit_aligned3d(const float* kept, const float* later, float thresh) {
+  const float l = fmaxf(0.f, __fsub_rn(fminf(kept[3], later[3]), fmaxf(kept[0], later[0])));
+  const float w = fmaxf(0.f, __fsub_rn(fminf(kept[4], later[4]), fmaxf(kept[1], later[1])));
+  const float h = fmaxf(0.f, __fsub_rn(fminf(kept[5], later[5]), fmaxf(kept[2], later[2])));
+  const float inter = __fmul_rn(__fmul_rn(l, w), h);
+  const float iou =
+      __fdiv_rn(inter, __fsub_rn(__fadd_rn(volume3d(kept), volume3d(later)), inter));
+  const float same = kept[6] == later[6] ? 1.f : 0.f;
+  return !(__fmul_rn(iou, same) <= thresh);
+}
+
 // The length of segment s as the kernels see it: clipped to the caller's bound and to the
 // rows that exist, so a bad offsets array cannot send an access out of `boxes` or `mask`.
 __device__ __forceinline__ int segment_rows(const int32_t* __restrict__ offsets, int s,
@@ -75,7 +96,7 @@ __global__ __launch_bounds__(kNmsTile) void nms_mask_kernel(
     const float* __restrict__ boxes, int ld, const int32_t* __restrict__ offsets, int total,
     int max_segment, const float* __restrict__ thresh, int words,
     unsigned long long* __restrict__ mask) {
-  constexpr int kCols = KIND == kCircle ? 2 : (KIND == kNormal ? 4 : 5);
+  constexpr int kCols = KIND == kAligned3d ? 7 : (KIND == kCircle ? 2 : (KIND == kNormal ? 4 : 5));
   const int ct = blockIdx.x, rt = blockIdx.y, s = blockIdx.z;
   if (ct < rt) return;
   int begin;
@@ -103,7 +124,9 @@ __global__ __launch_bounds__(kNmsTile) void nms_mask_kernel(
   unsigned long long bits = 0;
   for (int i = (rt == ct ? lane + 1 : 0); i < col_size; ++i) {
     bool hit;
-    if (KIND == kCircle) {
+    if (KIND == kAligned3d) {
+      hit = hit_aligned3d(mine, cols + i * kCols, th);
+    } else if (KIND == kCircle) {
       hit = circle_hit(mine, cols + i * kCols, th);
     } else if (KIND == kNormal) {
       hit = iou_normal(mine, cols + i * kCols) > th;
@@ -190,6 +213,36 @@ __global__ __launch_bounds__(256) void boxes_iou_bev_kernel(const float* __restr
   out[t] = iou_bev(ba, bb);
 }
 
+// The two launches of every NMS entry point, after its validation.
+int nms_launch(int kind, const float* boxes, int ld, const int32_t* offsets, int num_segments,
+               int total_boxes, int max_segment, const float* thresh, int post_max,
+               const int64_t* order, int64_t* keep, int keep_stride, int32_t* num_keep,
+               void* workspace, msmd_stream_t stream) {
+  const int bound = max_segment < total_boxes ? max_segment : total_boxes;
+  const int words = ceil_div(max_segment, kNmsTile);
+  hipStream_t st = (hipStream_t)stream;
+  unsigned long long* mask = (unsigned long long*)workspace;
+  const int tiles = ceil_div(bound, kNmsTile);
+  if (tiles > 0) {
+    const dim3 grid(tiles, tiles, num_segments), block(kNmsTile);
+    if (kind == kRotated)
+      MSMD_LAUNCH(nms_mask_kernel<kRotated>, grid, block, 0, st, boxes, ld, offsets, total_boxes,
+                  bound, thresh, words, mask);
+    else if (kind == kNormal)
+      MSMD_LAUNCH(nms_mask_kernel<kNormal>, grid, block, 0, st, boxes, ld, offsets, total_boxes,
+                  bound, thresh, words, mask);
+    else if (kind == kAligned3d)
+      MSMD_LAUNCH(nms_mask_kernel<kAligned3d>, grid, block, 0, st, boxes, ld, offsets, total_boxes,
+                  bound, thresh, words, mask);
+    else
+      MSMD_LAUNCH(nms_mask_kernel<kCircle>, grid, block, 0, st, boxes, ld, offsets, total_boxes,
+                  bound, thresh, words, mask);
+  }
+  MSMD_LAUNCH(nms_reduce_kernel, dim3(num_segments), dim3(kWave), 0, st, mask, offsets,
+              total_boxes, bound, words, post_max, order, keep, keep_stride, num_keep);
+  return launch_status();
+}
+
 }  // namespace
 }  // namespace msmd
 
@@ -228,26 +281,34 @@ MSMD_EXPORT int msmd_nms_batched_f32(int kind, const float* boxes, int ld, const
   if (!offsets || !thresh || !num_keep || (keep_stride > 0 && !keep)) return MSMD_ERR_INVALID_ARG;
   if (total_boxes > 0 && !boxes) return MSMD_ERR_INVALID_ARG;
   const int bound = max_segment < total_boxes ? max_segment : total_boxes;
-  const int words = ceil_div(max_segment, kNmsTile);
   if (bound > 0 && (!workspace || ((uintptr_t)workspace & 7) ||
                     workspace_bytes < msmd_nms_workspace_bytes(total_boxes, max_segment)))
     return MSMD_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  unsigned long long* mask = (unsigned long long*)workspace;
-  const int tiles = ceil_div(bound, kNmsTile);
-  if (tiles > 0) {
-    const dim3 grid(tiles, tiles, num_segments), block(kNmsTile);
-    if (kind == kRotated)
-      MSMD_LAUNCH(nms_mask_kernel<kRotated>, grid, block, 0, st, boxes, ld, offsets, total_boxes,
-                  bound, thresh, words, mask);
-    else if (kind == kNormal)
-      MSMD_LAUNCH(nms_mask_kernel<kNormal>, grid, block, 0, st, boxes, ld, offsets, total_boxes,
-                  bound, thresh, words, mask);
-    else
-      MSMD_LAUNCH(nms_mask_kernel<kCircle>, grid, block, 0, st, boxes, ld, offsets, total_boxes,
-                  bound, thresh, words, mask);
-  }
-  MSMD_LAUNCH(nms_reduce_kernel, dim3(num_segments), dim3(kWave), 0, st, mask, offsets,
-              total_boxes, bound, words, post_max, order, keep, keep_stride, num_keep);
-  return launch_status();
+  return nms_launch(kind, boxes, ld, offsets, num_segments, total_boxes, max_segment, thresh,
+                    post_max, order, keep, keep_stride, num_keep, workspace, stream);
+}
+
+MSMD_EXPORT size_t msmd_nms_aligned3d_workspace_bytes(int total_boxes, int max_segment) {
+  return msmd_nms_workspace_bytes(total_boxes, max_segment);
+}
+
+MSMD_EXPORT int msmd_nms_aligned3d_f32(const float* boxes, int ld, const int32_t* offsets,
+                                       int num_segments, int total_boxes, int max_segment,
+                                       const float* thresh, int post_max, const int64_t* order,
+                                       int64_t* keep, int keep_stride, int32_t* num_keep,
+                                       void* workspace, size_t workspace_bytes,
+                                       msmd_stream_t stream) {
+  if (num_segments < 0 || total_boxes < 0 || max_segment < 0 || post_max < 0 || keep_stride < 0)
+    return MSMD_ERR_INVALID_ARG;
+  if (max_segment > kNmsMaxSegment || ld < 7) return MSMD_ERR_INVALID_ARG;
+  if (num_segments > 65535) return MSMD_ERR_RANGE;
+  if (num_segments == 0) return MSMD_OK;
+  if (!offsets || !thresh || !num_keep || (keep_stride > 0 && !keep)) return MSMD_ERR_INVALID_ARG;
+  if (total_boxes > 0 && !boxes) return MSMD_ERR_INVALID_ARG;
+  const int bound = max_segment < total_boxes ? max_segment : total_boxes;
+  if (bound > 0 && (!workspace || ((uintptr_t)workspace & 7) ||
+                    workspace_bytes < msmd_nms_workspace_bytes(total_boxes, max_segment)))
+    return MSMD_ERR_WORKSPACE;
+  return nms_launch(kAligned3d, boxes, ld, offsets, num_segments, total_boxes, max_segment,
+                    thresh, post_max, order, keep, keep_stride, num_keep, workspace, stream);
 }

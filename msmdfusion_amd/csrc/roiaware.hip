@@ -40,6 +40,7 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "point_in_box.hpp"
 #include "scan.hpp"
 
 namespace msmd {
@@ -48,26 +49,9 @@ namespace {
 constexpr int kRoiMaxOut = 256;
 constexpr long kRoiMaxBlocks = (1L << 24) - 1;  // blocks of one (RoI, tile) launch
 
-struct Box {
-  float cx, cy, zb, w, l, h, rz;
-};
-__device__ __forceinline__ Box load_box(const float* __restrict__ b) {
-  return Box{b[0], b[1], b[2], b[3], b[4], b[5], b[6]};
-}
-
-// check_pt_in_box3d + lidar_to_local_coords, the reference's float/double mix
-__device__ __forceinline__ bool pt_in_box(float x, float y, float z, const Box& b, float& lx,
-                                          float& ly) {
-  const float cz = (float)((double)b.zb + (double)b.h / 2.0);
-  if ((double)fabsf(z - cz) > (double)b.h / 2.0) return false;
-  const float rot = (float)((double)b.rz + M_PI / 2);
-  const float ca = cosf(rot), sa = sinf(rot);
-  const float sx = x - b.cx, sy = y - b.cy;
-  lx = sx * ca + sy * (-sa);
-  ly = sx * sa + sy * ca;
-  const double hl = (double)b.l / 2.0, hw = (double)b.w / 2.0;
-  return (double)lx > -hl && (double)lx < hl && (double)ly > -hw && (double)ly < hw;
-}
+using pib::Box;
+using pib::load_box;
+using pib::pt_in_box;
 
 // min(max(int(q), 0), n - 1) for the finite q of a point inside; 0 for NaN
 __device__ __forceinline__ int clamp_idx(float q, int n) {

@@ -325,6 +325,54 @@ class VoxelNet(TransFusionDetector):
                 for b, s, l in self.bbox_head.get_bboxes(*outs, metas, rescale=rescale)]
 
 
+@DETECTORS.register_module()
+class VoteNet(nn.Module):
+    """mmdet3d/models/detectors/votenet.py on single_stage.py (SingleStage3DDetector): a
+    PointNet++ backbone built from BACKBONES and VoteHead, under the reference's attribute
+    names `backbone` and `bbox_head` (its state-dict prefixes).  Points arrive as a list of
+    equally long [N, C] tensors and are stacked, as there."""
+
+    def __init__(self, backbone, bbox_head=None, train_cfg=None, test_cfg=None, pretrained=None,
+                 init_cfg=None):
+        super().__init__()
+        from .registry import build_head
+        self.backbone = build_backbone(backbone)
+        self.bbox_head = bbox_head if isinstance(bbox_head, nn.Module) or bbox_head is None else \
+            build_head(dict(bbox_head, train_cfg=train_cfg, test_cfg=test_cfg))
+        self.train_cfg, self.test_cfg = train_cfg, test_cfg
+
+    @staticmethod
+    def _stack(points):
+        return points if torch.is_tensor(points) else torch.stack(list(points))
+
+    def extract_feat(self, points, img_metas=None):
+        """single_stage.py:52-59 (VoteNet has no neck)."""
+        return self.backbone(points)
+
+    def forward_train(self, points, img_metas=None, gt_bboxes_3d=None, gt_labels_3d=None,
+                      pts_semantic_mask=None, pts_instance_mask=None, gt_bboxes_ignore=None):
+        """votenet.py:26-62 -> the head's loss dict."""
+        points_cat = self._stack(points)
+        x = self.extract_feat(points_cat)
+        bbox_preds = self.bbox_head(x, self.train_cfg["sample_mod"])
+        return self.bbox_head.loss(bbox_preds, points_cat, gt_bboxes_3d, gt_labels_3d,
+                                   pts_semantic_mask, pts_instance_mask, img_metas,
+                                   gt_bboxes_ignore=gt_bboxes_ignore)
+
+    def simple_test(self, points, img_metas=None, imgs=None, rescale=False):
+        """votenet.py:64-84 (bbox3d2result's fields)."""
+        points_cat = self._stack(points)
+        x = self.extract_feat(points_cat)
+        bbox_preds = self.bbox_head(x, self.test_cfg["sample_mod"])
+        bbox_list = self.bbox_head.get_bboxes(points_cat, bbox_preds, img_metas, rescale=rescale)
+        return [dict(boxes_3d=b, scores_3d=s, labels_3d=l) for b, s, l in bbox_list]
+
+    def forward(self, points, img_metas=None, return_loss=False, **kw):
+        if return_loss:
+            return self.forward_train(points, img_metas, **kw)
+        return self.simple_test(points, img_metas, **kw)
+
+
 _WARNED = {}
 
 

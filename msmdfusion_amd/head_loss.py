@@ -67,6 +67,105 @@ class LiDARBoxes:
         return LiDARBoxes(self.tensor.to(device))
 
 
+class DepthBoxes:
+    """What VoteHead reads of DepthInstance3DBoxes (core/bbox/structures/depth_box3d.py,
+    base_box3d.py): `.tensor` [G, 7] = (x, y, z_bottom, x_size, y_size, z_size, yaw) in depth
+    coordinates (x right, y front, z up; yaw from +x towards +y), `.gravity_center`, `.corners`,
+    `.new_box`, `.to` and `.points_in_boxes`.  Six columns mean boxes without yaw (a zero yaw
+    is appended and with_yaw is False); `origin` is the relative position of the given centre
+    in the box, moved to the bottom centre (0.5, 0.5, 0) as base_box3d.py:36-65 does."""
+
+    def __init__(self, tensor, box_dim=7, with_yaw=True, origin=(0.5, 0.5, 0)):
+        device = tensor.device if isinstance(tensor, torch.Tensor) else torch.device("cpu")
+        tensor = torch.as_tensor(tensor, dtype=torch.float32, device=device)
+        if tensor.numel() == 0:
+            tensor = tensor.reshape((0, box_dim))
+        if tensor.dim() != 2 or tensor.size(-1) != box_dim:
+            raise ValueError("boxes must be [G, %d], got %s" % (box_dim, tuple(tensor.shape)))
+        if tensor.shape[-1] == 6:
+            tensor = torch.cat((tensor, tensor.new_zeros(tensor.shape[0], 1)), dim=-1)
+            self.box_dim, self.with_yaw = box_dim + 1, False
+        else:
+            self.box_dim, self.with_yaw = box_dim, with_yaw
+        self.tensor = tensor.clone()
+        if tuple(origin) != (0.5, 0.5, 0):
+            dst = self.tensor.new_tensor((0.5, 0.5, 0))
+            src = self.tensor.new_tensor(origin)
+            self.tensor[:, :3] += self.tensor[:, 3:6] * (dst - src)
+
+    def __len__(self):
+        return self.tensor.shape[0]
+
+    @property
+    def device(self):
+        return self.tensor.device
+
+    @property
+    def dims(self):
+        return self.tensor[:, 3:6]
+
+    @property
+    def bottom_center(self):
+        return self.tensor[:, :3]
+
+    @property
+    def gravity_center(self):
+        bottom_center = self.bottom_center
+        gravity_center = torch.zeros_like(bottom_center)
+        gravity_center[:, :2] = bottom_center[:, :2]
+        gravity_center[:, 2] = bottom_center[:, 2] + self.tensor[:, 5] * 0.5
+        return gravity_center
+
+    @property
+    def corners(self):
+        """[G, 8, 3] in the order of depth_box3d.py:46-84: the unit cube's corners about the
+        bottom centre, scaled, turned about z by the yaw, moved."""
+        dims = self.dims
+        unit = dims.new_tensor([[0, 0, 0], [0, 0, 1], [0, 1, 1], [0, 1, 0],
+                                [1, 0, 0], [1, 0, 1], [1, 1, 1], [1, 1, 0]])
+        unit = unit - dims.new_tensor([0.5, 0.5, 0])
+        corners = dims.view([-1, 1, 3]) * unit.reshape([1, 8, 3])
+        rot_sin, rot_cos = torch.sin(self.tensor[:, 6]), torch.cos(self.tensor[:, 6])
+        ones, zeros = torch.ones_like(rot_cos), torch.zeros_like(rot_cos)
+        rot_mat_t = torch.stack([torch.stack([rot_cos, -rot_sin, zeros]),
+                                 torch.stack([rot_sin, rot_cos, zeros]),
+                                 torch.stack([zeros, zeros, ones])])
+        corners = torch.einsum("aij,jka->aik", (corners, rot_mat_t))
+        corners += self.tensor[:, :3].view(-1, 1, 3)
+        return corners
+
+    def new_box(self, data):
+        new_tensor = self.tensor.new_tensor(data) if not isinstance(data, torch.Tensor) \
+            else data.to(self.device)
+        return DepthBoxes(new_tensor, box_dim=self.box_dim, with_yaw=self.with_yaw)
+
+    def to(self, device):
+        return DepthBoxes(self.tensor.to(device), box_dim=self.box_dim, with_yaw=self.with_yaw)
+
+    @staticmethod
+    def boxes_to_lidar(tensor):
+        """Box3DMode.convert(DEPTH -> LIDAR) (box_3d_mode.py:124-140) on [..., 7] rows: the
+        frame of the points-in-boxes predicate.  (x, y, z) -> (y, -x, z), sizes swapped, yaw kept."""
+        return torch.stack([tensor[..., 1], -tensor[..., 0], tensor[..., 2], tensor[..., 4],
+                            tensor[..., 3], tensor[..., 5], tensor[..., 6]], dim=-1)
+
+    @staticmethod
+    def points_to_lidar(points):
+        """depth_box3d.py:247-250 on [..., >= 3] points -> [..., 3]."""
+        return torch.stack([points[..., 1], -points[..., 0], points[..., 2]], dim=-1)
+
+    def points_in_boxes(self, points):
+        """depth_box3d.py:234-260: points [M, 3] (or [1, M, 3]) -> int32 [M, G], 1 where the
+        point lies in the box; both sides go to LiDAR coordinates first, as there."""
+        from . import kernels as K
+        if points.dim() == 3:
+            assert points.shape[0] == 1
+            points = points[0]
+        pts = self.points_to_lidar(points.float())[None].contiguous()
+        boxes = self.boxes_to_lidar(self.tensor.to(points.device))[None].contiguous()
+        return K.points_in_boxes(boxes, pts, True)[0]
+
+
 def _box_tensor(boxes):
     return boxes.tensor if hasattr(boxes, "tensor") else torch.as_tensor(boxes,
                                                                          dtype=torch.float32)

@@ -41,8 +41,9 @@ def nms_batched(kind, boxes, scores, offsets, thresh, pre_max=None, post_max=Non
     """NMS of S independent lists in one call, with no host read.
 
     kind: 'rotate' (boxes [N, 5] xyxyr, IoU > thresh), 'normal' (axis-aligned IoU of the
-    first four columns > thresh) or 'circle' (boxes [N, >= 2] centres, squared distance <=
-    thresh).  List s is rows offsets[s] .. offsets[s+1] of boxes / scores (offsets: int
+    first four columns > thresh), 'circle' (boxes [N, >= 2] centres, squared distance <=
+    thresh) or 'aligned3d' (boxes [N, 7]: x1, y1, z1, x2, y2, z2, class; a later box goes
+    unless 3-D IoU * same-class <= thresh, see aligned_3d_nms).  List s is rows offsets[s] .. offsets[s+1] of boxes / scores (offsets: int
     [S + 1] on the device).  thresh: a float, or one per list (sequence or tensor).
     pre_max: only the pre_max best boxes of a list take part; it also bounds the work, so
     it is required when N exceeds 16384 (a single list: its length is the bound).
@@ -102,3 +103,12 @@ def circle_nms(dets, thresh, post_max_size=83):
     tensor of kept indices (the reference takes a numpy array and returns a list).  The
     squared centre distance is evaluated in float32 exactly as numpy does there."""
     return _single("circle", dets[:, :2].contiguous(), dets[:, 2], thresh, None, post_max_size)
+
+
+def aligned_3d_nms(boxes, scores, classes, thresh):
+    """box3d_nms.aligned_3d_nms: boxes [N, 6] (x1, y1, z1, x2, y2, z2), scores [N], classes [N]
+    -> kept indices, best first.  A box is dropped by a kept, better one of its class whose IoU
+    with it exceeds thresh -- and, as in the reference's `iou <= thresh` selection, by ANY kept
+    better box when the IoU is NaN (two disjoint zero-volume boxes)."""
+    rows = torch.cat([boxes.float(), classes.to(boxes.device).float().reshape(-1, 1)], 1)
+    return _single("aligned3d", rows, scores, thresh, None, None)

@@ -1787,6 +1787,7 @@ def boxes_iou_bev(boxes_a, boxes_b):
 
 
 NMS_KINDS = {"rotate": 0, "rotated": 0, "normal": 1, "circle": 2}
+NMS_ALIGNED3D = "aligned3d"      # its own entry point (msmd_nms_aligned3d_f32), not a kind code
 NMS_MAX_SEGMENT = 16384
 
 
@@ -1797,7 +1798,8 @@ def nms_workspace_bytes(total_boxes, max_segment):
 def nms_segments(kind, boxes, offsets, thresh, max_segment, post_max=None, order=None,
                  keep=None, num_keep=None, workspace=None):
     """Greedy NMS of every segment in one call (two launches, nothing read back).
-    boxes [total, >= 5 | 4 | 2] float32, each segment (rows offsets[s] .. offsets[s+1], int32
+    boxes [total, >= 5 | 4 | 2] float32 ('aligned3d': [total, >= 7] rows x1, y1, z1, x2, y2, z2,
+    class), each segment (rows offsets[s] .. offsets[s+1], int32
     [S + 1] on the device) already in descending score order; only the first `max_segment`
     rows of a segment take part.  thresh: float32 [S] on the device.  order (optional, long
     [total]): the caller's sort permutation -- kept rows are then reported as order[row].
@@ -1805,7 +1807,7 @@ def nms_segments(kind, boxes, offsets, thresh, max_segment, post_max=None, order
     keep / num_keep / workspace (uint8, nms_workspace_bytes) may be passed in: with all three
     the call allocates nothing."""
     _need_cuda(boxes, offsets, thresh, order, keep, num_keep, workspace)
-    code = NMS_KINDS[kind]
+    code = None if kind == NMS_ALIGNED3D else NMS_KINDS[kind]
     if boxes.dtype != torch.float32 or boxes.dim() != 2 or not boxes.is_contiguous():
         raise ValueError("boxes must be a contiguous float32 [total, columns] tensor")
     if offsets.dtype != torch.int32 or thresh.dtype != torch.float32:
@@ -1834,11 +1836,118 @@ def nms_segments(kind, boxes, offsets, thresh, max_segment, post_max=None, order
     ws = _ws(nbytes, boxes.device) if workspace is None else workspace
     if ws.numel() * ws.element_size() < nbytes:
         raise ValueError("workspace holds %d bytes, %d needed" % (ws.numel(), nbytes))
+    if code is None:
+        check(lib.msmd_nms_aligned3d_f32(_p(boxes), boxes.shape[1], _p(offsets.contiguous()),
+                                         segments, total, max_segment, _p(thresh.contiguous()),
+                                         post, _p(order), _p(keep), stride, _p(num_keep), _p(ws),
+                                         nbytes, _stream()), "msmd_nms_aligned3d_f32")
+        return keep, num_keep
     check(lib.msmd_nms_batched_f32(code, _p(boxes), boxes.shape[1], _p(offsets.contiguous()),
                                    segments, total, max_segment, _p(thresh.contiguous()), post,
                                    _p(order), _p(keep), stride, _p(num_keep), _p(ws), nbytes,
                                    _stream()), "msmd_nms_batched_f32")
     return keep, num_keep
+
+
+# ------------------------------------------------ VoteNet ops (row n4)
+CHAMFER_MODES = {"l2": 0, "l1": 1, "smooth_l1": 2}
+
+
+def _chamfer_sets(src, dst):
+    _need_cuda(src, dst)
+    for t, what in ((src, "src"), (dst, "dst")):
+        _need_dtype(t, torch.float32, what)
+        if t.dim() != 3 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float32 [B, N, 3] tensor, got %s"
+                             % (what, tuple(t.shape)))
+    if src.shape[0] != dst.shape[0] or src.shape[2] != dst.shape[2]:
+        raise ValueError("src %s and dst %s need the same batch size and channels"
+                         % (tuple(src.shape), tuple(dst.shape)))
+    return src.shape[0], src.shape[1], dst.shape[1], src.shape[2]
+
+
+def chamfer_forward(src, dst, mode):
+    """src [B, N, 3], dst [B, M, 3] float32 -> (d1 [B, N], i1 long [B, N], d2 [B, M], i2 long
+    [B, M]): each point's smallest criterion distance to the other set and where it is
+    (torch.min's tie and NaN rules).  Two launches, no [N, M] buffer."""
+    b, n, m, c = _chamfer_sets(src, dst)
+    dev = src.device
+    d1 = torch.empty((b, n), dtype=torch.float32, device=dev)
+    d2 = torch.empty((b, m), dtype=torch.float32, device=dev)
+    i1 = torch.empty((b, n), dtype=torch.long, device=dev)
+    i2 = torch.empty((b, m), dtype=torch.long, device=dev)
+    check(lib.msmd_chamfer_fwd_f32(_p(src), _p(dst), b, n, m, c, CHAMFER_MODES[mode], _p(d1),
+                                   _p(i1), _p(d2), _p(i2), _stream()), "msmd_chamfer_fwd_f32")
+    return d1, i1, d2, i2
+
+
+def chamfer_backward(src, dst, g1, g2, i1, i2, mode, want_src=True, want_dst=True):
+    """-> (grad_src [B, N, 3] | None, grad_dst [B, M, 3] | None) for upstream g1 [B, N] and
+    g2 [B, M]; fixed summation order, no atomics."""
+    b, n, m, c = _chamfer_sets(src, dst)
+    _need_cuda(g1, g2, i1, i2)
+    for t, dt, shape, what in ((g1, torch.float32, (b, n), "g1"), (g2, torch.float32, (b, m), "g2"),
+                               (i1, torch.long, (b, n), "i1"), (i2, torch.long, (b, m), "i2")):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous %s %s tensor" % (what, dt, shape))
+    if not (want_src or want_dst):
+        return None, None
+    grad_src = torch.empty_like(src) if want_src else None
+    grad_dst = torch.empty_like(dst) if want_dst else None
+    check(lib.msmd_chamfer_bwd_f32(_p(src), _p(dst), _p(g1), _p(g2), _p(i1), _p(i2), b, n, m, c,
+                                   CHAMFER_MODES[mode], _p(grad_src), _p(grad_dst), _stream()),
+          "msmd_chamfer_bwd_f32")
+    return grad_src, grad_dst
+
+
+def vote_targets(points, point_offsets, boxes, centers, box_offsets, max_points=None,
+                 gt_per_seed=3):
+    """VoteHead.get_targets_single's box-form vote targets for every sample in one launch.
+    points float32 [P, >= 3] rows, sample s = rows point_offsets[s] .. point_offsets[s+1] (int32
+    [S + 1] on the device); boxes float32 [T, 7] in the points_in_boxes frame with gravity
+    `centers` [T, 3] and box_offsets likewise.  max_points: a host-known bound on a sample's
+    points (sizes the grid only).  -> (vote_targets float32 [P, 9], vote_mask long [P])."""
+    _need_cuda(points, point_offsets, boxes, centers, box_offsets)
+    for t, w, what in ((points, None, "points"), (boxes, 7, "boxes"), (centers, 3, "centers")):
+        _need_dtype(t, torch.float32, what)
+        if t.dim() != 2 or not t.is_contiguous() or (w is not None and t.shape[1] != w):
+            raise ValueError("%s must be a contiguous float32 [rows, %s] tensor, got %s"
+                             % (what, w or ">= 3", tuple(t.shape)))
+    if boxes.shape[0] != centers.shape[0]:
+        raise ValueError("one gravity centre per box")
+    for t in (point_offsets, box_offsets):
+        _need_dtype(t, torch.int32, "offsets")
+    samples = point_offsets.numel() - 1
+    if samples < 0 or box_offsets.numel() != samples + 1:
+        raise ValueError("point_offsets and box_offsets hold S + 1 entries each")
+    total = points.shape[0]
+    targets = torch.empty((total, 3 * int(gt_per_seed)), dtype=torch.float32, device=points.device)
+    mask = torch.empty((total,), dtype=torch.long, device=points.device)
+    check(lib.msmd_vote_targets_f32(_p(points), points.shape[1], _p(point_offsets.contiguous()),
+                                    _p(boxes), _p(centers), _p(box_offsets.contiguous()), samples,
+                                    total, boxes.shape[0],
+                                    total if max_points is None else int(max_points),
+                                    int(gt_per_seed), _p(targets), _p(mask), _stream()),
+          "msmd_vote_targets_f32")
+    return targets, mask
+
+
+def points_in_boxes_count(boxes, pts):
+    """boxes [B, T, 7], pts [B, M, >= 3] float32 -> int32 [B, T]: the sample's points inside
+    each box (the points_in_boxes predicate), without the [B, M, T] table."""
+    _need_cuda(boxes, pts)
+    for t, what in ((boxes, "boxes"), (pts, "points")):
+        _need_dtype(t, torch.float32, what)
+        if t.dim() != 3 or not t.is_contiguous():
+            raise RuntimeError("%s must be a contiguous [B, N, C] float32 tensor" % what)
+    if boxes.shape[2] != 7 or pts.shape[2] < 3 or boxes.shape[0] != pts.shape[0]:
+        raise RuntimeError("boxes [B, T, 7] and points [B, M, >= 3] expected, got %s and %s"
+                           % (tuple(boxes.shape), tuple(pts.shape)))
+    b, t, m = boxes.shape[0], boxes.shape[1], pts.shape[1]
+    count = torch.empty((b, t), dtype=torch.int32, device=pts.device)
+    check(lib.msmd_points_in_boxes_count_f32(_p(boxes), _p(pts), pts.shape[2], b, t, m, _p(count),
+                                             _stream()), "msmd_points_in_boxes_count_f32")
+    return count
 
 
 # ------------------------------------------------ Anchor3DHead targets / loss (row n3)
