@@ -1045,6 +1045,37 @@ int msmd_nn_assign(const int32_t* group_idx /* [m,nsample] ball-query out */,
                    int nsample, int nq, int32_t* query_nn /* [nq], -1 init by callee */,
                    int32_t* scratch /* [nq] */, msmd_stream_t stream);
 
+/* The whole chain behind FPS for all samples of a stage in one ragged launch set:
+ * nearest key of the representatives (or of the queries themselves) -> ball query ->
+ * assignment -> batch offsets -> pad rows.
+ * replaces: sparse_multimodal_encoder_painting.py:276-323 (fps_NN_fast behind its FPS call)
+ *           as SparseMultiModalEncoderPaint.grouped_sparse_conv composes it per sample
+ *           (:349-369), and the -1 rows of the padded only-2D voxels (:208-225)
+ * desc (device, int32 [4*b + 2]): query offsets [b+1] | key offsets [b+1] | mode [b] |
+ * base [b].  Sample s owns rows [q_off[s], q_off[s+1]) of query_bzyx and
+ * [k_off[s], k_off[s+1]) of key_bzyx (both (b,z,y,x) rows, 16-byte aligned; the batch
+ * column is skipped).  Modes: SKIP = every row -1; DIRECT = every query searches the
+ * keys itself (at most nq_max queries); CLUSTERED = the fps_num representatives
+ * fps_idx[s, :] (sample-local rows) search the keys, every query within `radius` of a
+ * representative that found a key (only the first max_cluster_samples hits in row order
+ * count) inherits it, the highest representative winning.  A valid row is
+ * base[s] + the key's sample-local index.  out: int64 [n_query + n_pad], the tail -1.
+ * nq_max / nk_max: the largest searching set (fps_num for a CLUSTERED sample) and the
+ * largest key set of the batch (host).  Exact for coordinates in [0, 32767] (the
+ * caller's contract) and dist_thresh, radius <= 2048 (else MSMD_ERR_UNSUPPORTED): see
+ * csrc/gma_nn.hip.  One fill and three kernels. */
+#define MSMD_NN_CHAIN_SKIP 0
+#define MSMD_NN_CHAIN_DIRECT 1
+#define MSMD_NN_CHAIN_CLUSTERED 2
+size_t msmd_gma_nn_chain_scratch_bytes(int b, int nq_max, int n_query);
+int msmd_gma_nn_chain(const int32_t* query_bzyx /* [n_query,4] */, int n_query,
+                      const int32_t* key_bzyx /* [n_key,4] */, int n_key,
+                      const int32_t* desc /* [4*b+2] device */, int b,
+                      const int32_t* fps_idx /* [b,fps_num] or NULL */, int fps_num,
+                      int nq_max, int nk_max, float dist_thresh, float radius,
+                      int max_cluster_samples, int n_pad, int64_t* out /* [n_query+n_pad] */,
+                      void* scratch, size_t scratch_bytes, msmd_stream_t stream);
+
 /* ------------------------------------------------------------------------ *
  * f3 (training half)  TransFusionHead.loss: target assignment and heat-map loss
  * replaces: iou3d_cuda.boxes_overlap_bev_gpu(boxes_a, boxes_b, ans_overlap)

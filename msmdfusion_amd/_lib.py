@@ -179,6 +179,9 @@ SIGNATURES = {
     "msmd_ball_query": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _vp]),
     "msmd_nn_search": (_i, [_vp, _i, _vp, _i, _f, _vp, _vp, _vp]),
     "msmd_nn_assign": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "msmd_gma_nn_chain_scratch_bytes": (_sz, [_i, _i, _i]),
+    "msmd_gma_nn_chain": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _f, _f, _i, _i, _vp, _vp,
+                               _sz, _vp]),
     "msmd_pillar_workspace_bytes": (_sz, [_i, _i, _i]),
     "msmd_pillar_moments_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _sz, _vp]),
     "msmd_pillar_pfn_fwd_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _i,

@@ -228,7 +228,7 @@ class SparseFusionPath(nn.Module):
                 with torch.cuda.stream(side):
                     mm.plan_stage_nn(plans[i], counts[i], B, self.fps_num_list[i],
                                      self.radius_list[i], self.max_cluster_samples_list[i],
-                                     self.dist_thresh_list[i])
+                                     self.dist_thresh_list[i], coord_bound=max(jobs[i][2]))
                     if nn_side_stream:
                         plans[i]["nn3"].record_stream(main)
                         # (read by the assembly's backward on the main stream: a caller that

@@ -2459,6 +2459,59 @@ def nn_assign(group_idx, rep_nn, nq):
     return out
 
 
+NN_CHAIN_SKIP, NN_CHAIN_DIRECT, NN_CHAIN_CLUSTERED = 0, 1, 2      # msmd_hip.h: MSMD_NN_CHAIN_*
+NN_CHAIN_KEYS = 256      # csrc/gma_nn.hip: kChainKeys, the keys one workgroup visits
+
+
+def gma_nn_chain_supported(coord_bound, dist_thresh, radius):
+    """Whether gma_nn_chain's integer distance order is exact (csrc/gma_nn.hip): every
+    coordinate below `coord_bound` <= 32768, dist_thresh and radius at most 2048 (radius > 0)."""
+    return (coord_bound is not None and int(coord_bound) <= 32768
+            and float(dist_thresh) <= 2048.0 and 0.0 < float(radius) <= 2048.0)
+
+
+def gma_nn_chain_desc(q_offsets, k_offsets, modes, bases, device):
+    """The per-sample descriptors of gma_nn_chain as one int32 device vector (one pinned,
+    non-blocking copy): query offsets [B+1] | key offsets [B+1] | mode [B] | base [B].
+    Its first B+1 entries are what furthest_point_sample_ragged takes as offsets."""
+    desc = torch.tensor(list(q_offsets) + list(k_offsets) + list(modes) + list(bases),
+                        dtype=torch.int32)
+    return desc.pin_memory().to(device, non_blocking=True)
+
+
+def _rows16(t):
+    """(b,z,y,x) rows as contiguous int32 whose first row is 16-byte aligned."""
+    t = t.contiguous().int()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def gma_nn_chain(query_bzyx, key_bzyx, desc, batch_size, fps_idx, fps_num, nq_max, nk_max,
+                 dist_thresh, radius, max_cluster_samples, n_pad=0):
+    """The neighbour search behind FPS for all samples of a stage (msmd_gma_nn_chain):
+    -> int64 [n_query + n_pad] rows of key_bzyx (base + sample-local nearest key), -1 = none.
+    desc: gma_nn_chain_desc(); fps_idx: int32 [B, fps_num] sample-local representatives
+    (None when no sample is CLUSTERED); nq_max / nk_max: host ints, the largest searching
+    set (fps_num for a CLUSTERED sample, its query count for a DIRECT one) and key set."""
+    _need_cuda(query_bzyx, key_bzyx, desc, fps_idx)
+    if not gma_nn_chain_supported(0, dist_thresh, radius):
+        raise ValueError("gma_nn_chain needs dist_thresh <= 2048 and radius <= 2048")
+    q, k = _rows16(query_bzyx), _rows16(key_bzyx)
+    nq, nk, b = q.shape[0], k.shape[0], int(batch_size)
+    assert q.shape[1:] == (4,) and k.shape[1:] == (4,) and desc.numel() == 4 * b + 2
+    assert desc.dtype == torch.int32 and desc.is_contiguous()
+    if fps_idx is not None:
+        assert fps_idx.dtype == torch.int32 and tuple(fps_idx.shape) == (b, int(fps_num))
+        fps_idx = fps_idx.contiguous()
+    out = torch.empty((nq + int(n_pad),), dtype=torch.long, device=q.device)
+    nbytes = lib.msmd_gma_nn_chain_scratch_bytes(b, int(nq_max), nq)
+    scratch = torch.empty((max(nbytes // 8 + 1, 1),), dtype=torch.int64, device=q.device)
+    check(lib.msmd_gma_nn_chain(_p(q), nq, _p(k), nk, _p(desc), b, _p(fps_idx), int(fps_num),
+                                int(nq_max), int(nk_max), float(dist_thresh), float(radius),
+                                int(max_cluster_samples), int(n_pad), _p(out), _p(scratch),
+                                scratch.numel() * 8, _stream()), "msmd_gma_nn_chain")
+    return out
+
+
 # ------------------------------------------------------------------ PointNet++ op family (n1)
 KNN_MAX_K = 128      # csrc/pointnet.hip: kKnnMaxK
 

@@ -164,13 +164,60 @@ class SparseMultiModalEncoderPaint(nn.Module):
         return torch.stack([(only_2d_bzyx[:, :1] == ids).sum(0), (voxel_3d_bzyx[:, :1] == ids).sum(0)])
 
     def nearest_3d_of_only_2d(self, only_2d_bzyx, voxel_3d_bzyx, batch_size, fps_num, radius,
-                              max_cluster_samples, dist_thresh, counts=None):
+                              max_cluster_samples, dist_thresh, counts=None, coord_bound=None,
+                              n_pad=0):
         """Per sample nearest LiDAR voxel of every only-2D voxel (:349-369);
-        returns global row indices into voxel_3D, -1 = unassigned.  Rows of both
+        returns global row indices into voxel_3D, -1 = unassigned, and `n_pad` more -1 rows
+        behind them (the padded only-2D voxels, :208-225).  Rows of both
         tensors are grouped by sample (they always are: voxelize concatenates
         samples in order).  One host read (the per-sample counts; none when the
         caller passes them as nested lists); when every sample needs the FPS
-        path, all samples' FPS run in ONE ragged launch."""
+        path, all samples' FPS run in ONE ragged launch, and everything behind FPS is one
+        native call for the whole batch (kernels.gma_nn_chain).
+        coord_bound: an upper bound of every coordinate (the largest spatial extent the caller
+        holds).  The one-call chain orders keys by integer squared distance, which is exact
+        for coordinates below 32768 and dist_thresh, radius <= 2048; outside that, or
+        without a bound, the per-sample entries run instead."""
+        if not K.gma_nn_chain_supported(coord_bound, dist_thresh, radius):
+            out = self._nearest_3d_per_sample(only_2d_bzyx, voxel_3d_bzyx, batch_size, fps_num,
+                                              radius, max_cluster_samples, dist_thresh, counts)
+            return torch.cat([out, out.new_full((n_pad,), -1)]) if n_pad else out
+        dev = only_2d_bzyx.device
+        if counts is None:
+            counts = self.sample_counts(only_2d_bzyx, voxel_3d_bzyx, batch_size).tolist()
+        c2, c3 = counts
+        o2, o3, modes, bases = [0], [0], [], []
+        for b in range(batch_size):
+            o2.append(o2[-1] + c2[b])
+            o3.append(o3[-1] + c3[b])
+            modes.append(K.NN_CHAIN_SKIP if not (c2[b] and c3[b]) else
+                         K.NN_CHAIN_DIRECT if c2[b] <= fps_num else K.NN_CHAIN_CLUSTERED)
+            # cumulative offsets; the reference adds the previous sample's count only (B.4)
+            bases.append((c3[b - 1] if b > 0 else 0) if self.reference_quirks else o3[b])
+        # pinned + non_blocking: a pageable copy would block the host until the stream
+        # (the previous stage's 6 ms FPS, when this runs on the search stream) drains
+        desc = K.gma_nn_chain_desc(o2, o3, modes, bases, dev)
+        big = [b for b in range(batch_size) if modes[b] == K.NN_CHAIN_CLUSTERED]
+        rep_all = None
+        if big:
+            q_f = only_2d_bzyx[:, 1:].float()
+            if len(big) == batch_size and batch_size > 1:   # the common case at stages 0/1
+                rep_all = K.furthest_point_sample_ragged(q_f, desc[:batch_size + 1], max(c2),
+                                                         fps_num)
+            else:
+                rep_all = torch.zeros((batch_size, fps_num), dtype=torch.int32, device=dev)
+                for b in big:
+                    rep_all[b] = K.furthest_point_sample(q_f[None, o2[b]:o2[b + 1]], fps_num)[0]
+        nq_max = max(fps_num if m == K.NN_CHAIN_CLUSTERED else c2[b] if m == K.NN_CHAIN_DIRECT
+                     else 0 for b, m in enumerate(modes))
+        nk_max = max(c3[b] if m != K.NN_CHAIN_SKIP else 0 for b, m in enumerate(modes))
+        return K.gma_nn_chain(only_2d_bzyx, voxel_3d_bzyx, desc, batch_size, rep_all, fps_num,
+                              nq_max, nk_max, dist_thresh, radius, max_cluster_samples, n_pad)
+
+    def _nearest_3d_per_sample(self, only_2d_bzyx, voxel_3d_bzyx, batch_size, fps_num, radius,
+                               max_cluster_samples, dist_thresh, counts=None):
+        """nearest_3d_of_only_2d through the per-sample entries (nn_search / ball_query /
+        nn_assign): the path outside the one-call chain's precondition."""
         dev = only_2d_bzyx.device
         out = torch.full((only_2d_bzyx.shape[0],), -1, dtype=torch.long, device=dev)
         if counts is None:
@@ -263,14 +310,14 @@ class SparseMultiModalEncoderPaint(nn.Module):
         return plan
 
     def plan_stage_nn(self, plan, counts, batch_size, fps_num, radius, max_cluster_samples,
-                      dist_thresh):
+                      dist_thresh, coord_bound=None):
         """The neighbour search of a planned stage (no host read: `counts` are the
         nested lists already on the host).  Stream-agnostic: the fusion path
-        enqueues it on a side stream under the LiDAR encoder's forward pass."""
+        enqueues it on a side stream under the LiDAR encoder's forward pass.
+        coord_bound: see nearest_3d_of_only_2d."""
         nn3 = self.nearest_3d_of_only_2d(plan["o2_bzyx"], plan["idx3"], batch_size, fps_num,
-                                         radius, max_cluster_samples, dist_thresh, counts=counts)
-        if plan["n_pad"]:
-            nn3 = torch.cat([nn3, nn3.new_full((plan["n_pad"],), -1)])
+                                         radius, max_cluster_samples, dist_thresh, counts=counts,
+                                         coord_bound=coord_bound, n_pad=plan["n_pad"])
         plan["nn3"] = nn3
         # the rows of each nearest voxel, for the assembly's backward (no atomics there)
         n_raw = plan["o2_bzyx"].shape[0]
@@ -402,7 +449,8 @@ class SparseMultiModalEncoderPaint(nn.Module):
         if plan is None:        # index-only work not done ahead of time: do it here
             plan = self.plan_stage_rows(voxel_3D.indices, voxel_2D.indices, B)
             self.plan_stage_nn(plan, plan["counts"].tolist(), B, fps_num, radius,
-                               max_cluster_samples, dist_thresh)
+                               max_cluster_samples, dist_thresh,
+                               coord_bound=max(*voxel_3D.spatial_shape, *voxel_2D.spatial_shape))
         elif plan.get("ready") is not None:     # computed on another stream
             torch.cuda.current_stream().wait_event(plan["ready"])
         only_3D_rows, only_2D_rows = plan["only_3D_rows"], plan["only_2D_rows"]
