@@ -1448,6 +1448,65 @@ int msmd_nms_aligned3d_f32(const float* boxes /* [total_boxes, ld >= 7] */, int 
                            int32_t* num_keep /* [num_segments] */, void* workspace,
                            size_t workspace_bytes, msmd_stream_t stream);
 
+/* ---- 3DSSD (COVERAGE n5) ------------------------------------------------------------------
+ * Candidate targets of SSD3DHead for the whole batch in one launch: what
+ * SSD3DHead.get_targets_single and _assign_targets_by_points_inside compute per sample
+ * (mmdet3d/models/dense_heads/ssd_3d_head.py:307-437, 545-572: about sixty tensor ops, two
+ * points_in_boxes_gpu launches, a gt[valid] compaction and a host read per sample).
+ * Sample s owns candidate rows s * num_candidates .. and box rows box_offsets[s] ..
+ * box_offsets[s+1] of gt_boxes / vote_boxes / labels / box_table / dir_class.  Both box tables are
+ * in the frame of msmd_points_in_boxes_f32 and tested with its predicate; a row whose label is
+ * -1 does not exist.  box_table row (table_width must be 33): gravity centre (3), half sizes
+ * (3), direction residual (1), sin and cos of -yaw (2), the 8 x 3 corners (24), all computed by
+ * the caller.  seeds: sample s starts at seeds + s * seed_stride floats, 3 per candidate.
+ * Per candidate, with `a` = the first existing box (ascending) holding the aggregated point, or
+ * the sample's LAST existing box when none does (inside = a box holds it):
+ *   center_targets / size_targets / dir_class_targets / dir_res_targets / mask_targets / corners
+ *     = copies from box a (centre absolute);
+ *   positive = inside && |p - (centre + (0, 0, half_z))| < pos_distance_thr; negative = !inside;
+ *   centerness[k] = c * (k == label ? 1 : 0), c = clamp(cbrt(clamp(l * w * h, 0)), 0, 1) with the
+ *     min / max ratios of the six clamped face distances of the point turned by -yaw, float32,
+ *     one rounding per operation, NaN propagated as torch.clamp / min / max do;
+ *   vote_mask / vote_targets: the same rule with vote_boxes on the seed point,
+ *     vote_targets = centre(box) - seed.
+ * A sample without an existing row gets zeros everywhere and negative = 1.  Masks are bytes
+ * (0 / 1).  Every output row is written; nothing is read back; the launch shape depends on the
+ * arguments only. */
+int msmd_ssd3d_gt_chunk(void); /* boxes per LDS chunk */
+int msmd_ssd3d_targets_f32(const float* aggregated /* [batch,num_candidates,3] */,
+                           const float* seeds, int64_t seed_stride,
+                           const float* gt_boxes /* [total_boxes,7] */,
+                           const float* vote_boxes /* [total_boxes,7] */,
+                           const int64_t* labels /* [total_boxes] */,
+                           const int32_t* box_offsets /* [batch+1] */,
+                           const float* box_table /* [total_boxes,table_width] */,
+                           int table_width, const int64_t* dir_class /* [total_boxes] */,
+                           int batch, int num_candidates, int total_boxes, int num_classes,
+                           float pos_distance_thr, float* vote_targets /* [batch,n,3] */,
+                           float* center_targets /* [batch,n,3] */,
+                           float* size_targets /* [batch,n,3] */,
+                           int64_t* dir_class_targets /* [batch,n] */,
+                           float* dir_res_targets /* [batch,n] */,
+                           int64_t* mask_targets /* [batch,n] */,
+                           float* centerness /* [batch,n,num_classes] */,
+                           float* corners /* [batch,n,8,3] */, uint8_t* vote_mask /* [batch,n] */,
+                           uint8_t* positive_mask /* [batch,n] */,
+                           uint8_t* negative_mask /* [batch,n] */, msmd_stream_t stream);
+/* mmcv.ops.nms's pair test (mmcv 1.x nms_cuda_kernel.cuh, offset 0) over segments, the kernel
+ * behind batched_nms (ssd_3d_head.py:512-515).  Rows (x1, y1, x2, y2), already shifted by
+ * class * (max coordinate + 1) as batched_nms does, in descending score order.  A kept row i
+ * suppresses a later row j when inter > thresh[s] * (area_i + area_j - inter), inter = the
+ * product of the two fmaxf(min(hi) - max(lo), 0) extents, float32, one rounding per operation:
+ * no division and no floor on the union.  Everything else is msmd_nms_batched_f32's; the
+ * workspace is msmd_nms_workspace_bytes. */
+int msmd_nms_mmcv_f32(const float* boxes /* [total_boxes, ld >= 4] */, int ld,
+                      const int32_t* offsets /* [num_segments + 1] */, int num_segments,
+                      int total_boxes, int max_segment, const float* thresh /* [num_segments] */,
+                      int post_max, const int64_t* order /* [total_boxes] or NULL */,
+                      int64_t* keep /* [num_segments, keep_stride] */, int keep_stride,
+                      int32_t* num_keep /* [num_segments] */, void* workspace,
+                      size_t workspace_bytes, msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

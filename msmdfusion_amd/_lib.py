@@ -213,6 +213,10 @@ SIGNATURES = {
     "msmd_nms_aligned3d_workspace_bytes": (_sz, [_i, _i]),
     "msmd_nms_aligned3d_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _sz,
                                     _vp]),
+    "msmd_ssd3d_gt_chunk": (_i, []),
+    "msmd_ssd3d_targets_f32": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i,
+                                    _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msmd_nms_mmcv_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -383,6 +383,55 @@ VOTENET_SUNRGBD = _votenet(10, 12, True, _SUNRGBD_MEAN_SIZES)
 VOTENET_SCANNET = _votenet(18, 1, False, _SCANNET_MEAN_SIZES)
 
 
+# ---------------------------------------------------------------------------------------------
+# 3DSSD (configs/_base_/models/3dssd.py under configs/3dssd/3dssd_kitti-3d-car.py):
+# PointNet2SAMSG + SSD3DHead, one class.  tests/golden/reference_3dssd_config.json holds the
+# reference's values.
+_SSD3D_BN1D = dict(type="BN1d", eps=1e-3, momentum=0.1)
+_SSD3D_BN2D = dict(type="BN2d", eps=1e-3, momentum=0.1)
+_SSD3D_SUM = dict(type="SmoothL1Loss", reduction="sum", loss_weight=1.0)
+SSD3D_KITTI_CAR = dict(model=dict(
+    type="SSD3DNet",
+    backbone=dict(
+        type="PointNet2SAMSG", in_channels=4, num_points=(4096, 512, (256, 256)),
+        radii=((0.2, 0.4, 0.8), (0.4, 0.8, 1.6), (1.6, 3.2, 4.8)),
+        num_samples=((32, 32, 64), (32, 32, 64), (32, 32, 32)),
+        sa_channels=(((16, 16, 32), (16, 16, 32), (32, 32, 64)),
+                     ((64, 64, 128), (64, 64, 128), (64, 96, 128)),
+                     ((128, 128, 256), (128, 192, 256), (128, 256, 256))),
+        aggregation_channels=(64, 128, 256),
+        fps_mods=(("D-FPS"), ("FS"), ("F-FPS", "D-FPS")),
+        fps_sample_range_lists=((-1), (-1), (512, -1)),
+        norm_cfg=dict(_SSD3D_BN2D),
+        sa_cfg=dict(type="PointSAModuleMSG", pool_mod="max", use_xyz=True, normalize_xyz=False)),
+    bbox_head=dict(
+        type="SSD3DHead", in_channels=256,
+        vote_module_cfg=dict(
+            in_channels=256, num_points=256, gt_per_seed=1, conv_channels=(128,),
+            conv_cfg=dict(type="Conv1d"), norm_cfg=dict(_SSD3D_BN1D), with_res_feat=False,
+            vote_xyz_range=(3.0, 3.0, 2.0)),
+        vote_aggregation_cfg=dict(
+            type="PointSAModuleMSG", num_point=256, radii=(4.8, 6.4), sample_nums=(16, 32),
+            mlp_channels=((256, 256, 256, 512), (256, 256, 512, 1024)),
+            norm_cfg=dict(_SSD3D_BN2D), use_xyz=True, normalize_xyz=False, bias=True),
+        pred_layer_cfg=dict(
+            in_channels=1536, shared_conv_channels=(512, 128), cls_conv_channels=(128,),
+            reg_conv_channels=(128,), conv_cfg=dict(type="Conv1d"), norm_cfg=dict(_SSD3D_BN1D),
+            bias=True),
+        conv_cfg=dict(type="Conv1d"), norm_cfg=dict(_SSD3D_BN1D),
+        objectness_loss=dict(type="CrossEntropyLoss", use_sigmoid=True, reduction="sum",
+                             loss_weight=1.0),
+        center_loss=dict(_SSD3D_SUM), dir_class_loss=dict(type="CrossEntropyLoss",
+                                                          reduction="sum", loss_weight=1.0),
+        dir_res_loss=dict(_SSD3D_SUM), size_res_loss=dict(_SSD3D_SUM),
+        corner_loss=dict(_SSD3D_SUM), vote_loss=dict(_SSD3D_SUM),
+        num_classes=1,
+        bbox_coder=dict(type="AnchorFreeBBoxCoder", num_dir_bins=12, with_rot=True)),
+    train_cfg=dict(sample_mod="spec", pos_distance_thr=10.0, expand_dims_length=0.05),
+    test_cfg=dict(nms_cfg=dict(type="nms", iou_thr=0.1), sample_mod="spec", score_thr=0.0,
+                  per_class_proposal=True, max_output_num=100)))
+
+
 def build_hot_path(cfg):
     """(Voxelization, voxel encoder, SparseEncoder, multimodal encoder | None) from one of
     the dicts above -- what MSMDFusionDetector.__init__ / MVXTwoStageDetector.__init__ build

@@ -1,6 +1,7 @@
 // nms.hip -- the iou3d op family's suppression side (COVERAGE n2): rotated, axis-aligned and
 // circle NMS, batched over segments, with the greedy reduction on the device; and the
-// class-aware axis-aligned 3-D NMS of the VoteNet family (COVERAGE n4) on the same two kernels.
+// class-aware axis-aligned 3-D NMS of the VoteNet family (COVERAGE n4) and mmcv's `nms` pair
+// test for 3DSSD's batched_nms (COVERAGE n5) on the same two kernels.
 //
 //   nms_mask_kernel    ops/iou3d/src/iou3d_kernel.cu nms_kernel / nms_normal_kernel (:283-419)
 //                      and the pair test of core/post_processing/box3d_nms.py:158-181
@@ -12,6 +13,8 @@
 //   boxes_iou_bev      iou3d_kernel.cu boxes_iou_bev_kernel (:269-281).
 //   hit_aligned3d      the pair test of core/post_processing/box3d_nms.py:91-138
 //                      (aligned_3d_nms, a Python while loop with one host read per kept box).
+//   hit_mmcv           mmcv 1.x ops/csrc/nms_cuda_kernel.cuh devIoU with offset = 0, the pair test
+//                      behind mmcv.ops.batched_nms (ssd_3d_head.py:512-515, one call per sample).
 //
 // A segment is one (task, sample) list of boxes, sorted by descending score by the caller and
 // addressed through a CSR offsets array that stays on the device.  The host only knows an
@@ -30,7 +33,7 @@ constexpr int kNmsTile = 64;                 // rows / columns per tile = bits p
 constexpr int kNmsMaxSegment = 16384;        // removed bitset: 256 words = 2 KB of LDS
 constexpr int kNmsMaxWords = kNmsMaxSegment / kNmsTile;
 
-enum { kRotated = 0, kNormal = 1, kCircle = 2, kAligned3d = 3 };
+enum { kRotated = 0, kNormal = 1, kCircle = 2, kAligned3d = 3, kMmcv = 4 };
 
 // iou3d_kernel.cu:244-251
 __device__ __forceinline__ float iou_bev(const Box& a, const Box& b) {
@@ -77,6 +80,20 @@ __device__ __forceinline__ bool hit_aligned3d(const float* kept, const float* la
   return !(__fmul_rn(iou, same) <= thresh);
 }
 
+// mmcv devIoU, offset 0, on rows (x1, y1, x2, y2) the caller has already shifted by class: the
+// multiply form `inter > thr * (area_i + area_j - inter)`.  Unlike iou_normal there is no
+// division and no 1e-8 floor, so two zero-area boxes give 0 > 0: no suppression.
+__device__ __forceinline__ bool hit_mmcv(const float* kept, const float* later, float thresh) {
+  const float left = fmaxf(kept[0], later[0]), right = fminf(kept[2], later[2]);
+  const float top = fmaxf(kept[1], later[1]), bottom = fminf(kept[3], later[3]);
+  const float width = fmaxf(__fsub_rn(right, left), 0.f);
+  const float height = fmaxf(__fsub_rn(bottom, top), 0.f);
+  const float inter = __fmul_rn(width, height);
+  const float sa = __fmul_rn(__fsub_rn(kept[2], kept[0]), __fsub_rn(kept[3], kept[1]));
+  const float sb = __fmul_rn(__fsub_rn(later[2], later[0]), __fsub_rn(later[3], later[1]));
+  return inter > __fmul_rn(thresh, __fsub_rn(__fadd_rn(sa, sb), inter));
+}
+
 // The length of segment s as the kernels see it: clipped to the caller's bound and to the
 // rows that exist, so a bad offsets array cannot send an access out of `boxes` or `mask`.
 __device__ __forceinline__ int segment_rows(const int32_t* __restrict__ offsets, int s,
@@ -96,7 +113,8 @@ __global__ __launch_bounds__(kNmsTile) void nms_mask_kernel(
     const float* __restrict__ boxes, int ld, const int32_t* __restrict__ offsets, int total,
     int max_segment, const float* __restrict__ thresh, int words,
     unsigned long long* __restrict__ mask) {
-  constexpr int kCols = KIND == kAligned3d ? 7 : (KIND == kCircle ? 2 : (KIND == kNormal ? 4 : 5));
+  constexpr int kCols =
+      KIND == kAligned3d ? 7 : (KIND == kCircle ? 2 : (KIND == kNormal || KIND == kMmcv ? 4 : 5));
   const int ct = blockIdx.x, rt = blockIdx.y, s = blockIdx.z;
   if (ct < rt) return;
   int begin;
@@ -126,6 +144,8 @@ __global__ __launch_bounds__(kNmsTile) void nms_mask_kernel(
     bool hit;
     if (KIND == kAligned3d) {
       hit = hit_aligned3d(mine, cols + i * kCols, th);
+    } else if (KIND == kMmcv) {
+      hit = hit_mmcv(mine, cols + i * kCols, th);
     } else if (KIND == kCircle) {
       hit = circle_hit(mine, cols + i * kCols, th);
     } else if (KIND == kNormal) {
@@ -234,6 +254,9 @@ int nms_launch(int kind, const float* boxes, int ld, const int32_t* offsets, int
     else if (kind == kAligned3d)
       MSMD_LAUNCH(nms_mask_kernel<kAligned3d>, grid, block, 0, st, boxes, ld, offsets, total_boxes,
                   bound, thresh, words, mask);
+    else if (kind == kMmcv)
+      MSMD_LAUNCH(nms_mask_kernel<kMmcv>, grid, block, 0, st, boxes, ld, offsets, total_boxes,
+                  bound, thresh, words, mask);
     else
       MSMD_LAUNCH(nms_mask_kernel<kCircle>, grid, block, 0, st, boxes, ld, offsets, total_boxes,
                   bound, thresh, words, mask);
@@ -311,4 +334,24 @@ MSMD_EXPORT int msmd_nms_aligned3d_f32(const float* boxes, int ld, const int32_t
     return MSMD_ERR_WORKSPACE;
   return nms_launch(kAligned3d, boxes, ld, offsets, num_segments, total_boxes, max_segment,
                     thresh, post_max, order, keep, keep_stride, num_keep, workspace, stream);
+}
+
+MSMD_EXPORT int msmd_nms_mmcv_f32(const float* boxes, int ld, const int32_t* offsets,
+                                  int num_segments, int total_boxes, int max_segment,
+                                  const float* thresh, int post_max, const int64_t* order,
+                                  int64_t* keep, int keep_stride, int32_t* num_keep,
+                                  void* workspace, size_t workspace_bytes, msmd_stream_t stream) {
+  if (num_segments < 0 || total_boxes < 0 || max_segment < 0 || post_max < 0 || keep_stride < 0)
+    return MSMD_ERR_INVALID_ARG;
+  if (max_segment > kNmsMaxSegment || ld < 4) return MSMD_ERR_INVALID_ARG;
+  if (num_segments > 65535) return MSMD_ERR_RANGE;
+  if (num_segments == 0) return MSMD_OK;
+  if (!offsets || !thresh || !num_keep || (keep_stride > 0 && !keep)) return MSMD_ERR_INVALID_ARG;
+  if (total_boxes > 0 && !boxes) return MSMD_ERR_INVALID_ARG;
+  const int bound = max_segment < total_boxes ? max_segment : total_boxes;
+  if (bound > 0 && (!workspace || ((uintptr_t)workspace & 7) ||
+                    workspace_bytes < msmd_nms_workspace_bytes(total_boxes, max_segment)))
+    return MSMD_ERR_WORKSPACE;
+  return nms_launch(kMmcv, boxes, ld, offsets, num_segments, total_boxes, max_segment, thresh,
+                    post_max, order, keep, keep_stride, num_keep, workspace, stream);
 }

@@ -373,6 +373,12 @@ class VoteNet(nn.Module):
         return self.simple_test(points, img_metas, **kw)
 
 
+@DETECTORS.register_module()
+class SSD3DNet(VoteNet):
+    """mmdet3d/models/detectors/ssd3dnet.py: VoteNet's flow with a PointNet2SAMSG backbone and
+    SSD3DHead."""
+
+
 _WARNED = {}
 
 

@@ -42,29 +42,110 @@ except ImportError:                               # the reference defers the sam
 
 
 # ------------------------------------------------------------------ boxes
-class LiDARBoxes:
-    """The two members of LiDARInstance3DBoxes the head's loss reads
-    (core/bbox/structures/lidar_box3d.py:36-43, base_box3d.py): `.tensor` [G, 7+] =
-    (x, y, z_bottom, dx, dy, dz, yaw, ...) and `.gravity_center`."""
+def _constant(like, values):
+    """A small constant beside `like`, uploaded without blocking (Tensor.new_tensor on a device
+    tensor is a blocking copy)."""
+    return torch.tensor(values, dtype=like.dtype).to(like.device, non_blocking=True)
 
-    def __init__(self, tensor, box_dim=None):
+
+class LiDARBoxes:
+    """What the heads read of LiDARInstance3DBoxes (core/bbox/structures/lidar_box3d.py,
+    base_box3d.py): `.tensor` [G, 7+] = (x, y, z_bottom, dx, dy, dz, yaw, ...),
+    `.gravity_center`, and for SSD3DHead `.dims`, `.yaw`, `.bottom_center`, `.corners`,
+    `.enlarged_box`, `.new_box`, indexing and `.points_in_boxes`.  `origin` is the relative
+    position of the given centre in the box; anything but the bottom centre (0.5, 0.5, 0) is
+    moved there on a copy (base_box3d.py:36-65).  With the default origin the tensor is kept as
+    given, not copied."""
+
+    def __init__(self, tensor, box_dim=None, with_yaw=True, origin=(0.5, 0.5, 0)):
         tensor = torch.as_tensor(tensor, dtype=torch.float32)
         if tensor.numel() == 0:
             tensor = tensor.reshape(0, box_dim or 7)
         if tensor.dim() != 2 or tensor.shape[1] < 7:
             raise ValueError("boxes must be [G, >=7], got %s" % (tuple(tensor.shape),))
+        self.with_yaw = with_yaw
+        if tuple(origin) != (0.5, 0.5, 0):
+            tensor = tensor.clone()
+            dst, src = _constant(tensor, (0.5, 0.5, 0)), _constant(tensor, tuple(origin))
+            tensor[:, :3] += tensor[:, 3:6] * (dst - src)
         self.tensor = tensor
 
     def __len__(self):
         return self.tensor.shape[0]
 
     @property
+    def box_dim(self):
+        return self.tensor.shape[1]
+
+    @property
+    def device(self):
+        return self.tensor.device
+
+    @property
+    def dims(self):
+        return self.tensor[:, 3:6]
+
+    @property
+    def yaw(self):
+        return self.tensor[:, 6]
+
+    @property
+    def bottom_center(self):
+        return self.tensor[:, :3]
+
+    @property
     def gravity_center(self):
         t = self.tensor
         return torch.cat([t[:, :2], (t[:, 2] + t[:, 5] * 0.5)[:, None]], dim=1)
 
+    @property
+    def corners(self):
+        """[G, 8, 3] in the order of lidar_box3d.py:46-84 (x0y0z0, x0y0z1, x0y1z1, x0y1z0,
+        x1y0z0, x1y0z1, x1y1z1, x1y1z0): the unit cube about the bottom centre, scaled, turned
+        about z by the yaw (rotation_3d_in_axis's einsum), moved."""
+        dims = self.dims
+        unit = _constant(dims, [[-0.5, -0.5, 0], [-0.5, -0.5, 1], [-0.5, 0.5, 1], [-0.5, 0.5, 0],
+                                [0.5, -0.5, 0], [0.5, -0.5, 1], [0.5, 0.5, 1], [0.5, 0.5, 0]])
+        corners = dims.view([-1, 1, 3]) * unit.reshape([1, 8, 3])
+        rot_sin, rot_cos = torch.sin(self.tensor[:, 6]), torch.cos(self.tensor[:, 6])
+        ones, zeros = torch.ones_like(rot_cos), torch.zeros_like(rot_cos)
+        rot_mat_t = torch.stack([torch.stack([rot_cos, -rot_sin, zeros]),
+                                 torch.stack([rot_sin, rot_cos, zeros]),
+                                 torch.stack([zeros, zeros, ones])])
+        corners = torch.einsum("aij,jka->aik", (corners, rot_mat_t))
+        corners += self.tensor[:, :3].view(-1, 1, 3)
+        return corners
+
+    def __getitem__(self, item):
+        """base_box3d.py:311-333: an int gives one box, anything else a selection of rows."""
+        if isinstance(item, int):
+            return LiDARBoxes(self.tensor[item].view(1, -1), with_yaw=self.with_yaw)
+        picked = self.tensor[item]
+        assert picked.dim() == 2, "Indexing on boxes with %r failed to return a matrix" % (item,)
+        return LiDARBoxes(picked, box_dim=self.box_dim, with_yaw=self.with_yaw)
+
+    def new_box(self, data):
+        """base_box3d.py:440-457: boxes of this type and device from other data."""
+        new_tensor = self.tensor.new_tensor(data) if not isinstance(data, torch.Tensor) \
+            else data.to(self.device)
+        return LiDARBoxes(new_tensor, box_dim=self.box_dim, with_yaw=self.with_yaw)
+
+    def enlarged_box(self, extra_width):
+        """lidar_box3d.py:227-240: every size grows by 2 * extra_width, the bottom drops by it."""
+        enlarged = self.tensor.clone()
+        enlarged[:, 3:6] += extra_width * 2
+        enlarged[:, 2] -= extra_width
+        return self.new_box(enlarged)
+
+    def points_in_boxes(self, points):
+        """lidar_box3d.py:242-257: points [M, 3] -> int32 [M], the FIRST box holding each point
+        or -1 (points_in_boxes_gpu's `break`)."""
+        from . import kernels as K
+        boxes = self.tensor[:, :7].to(points.device)[None].contiguous()
+        return K.points_in_boxes(boxes, points.float()[None].contiguous(), False)[0]
+
     def to(self, device):
-        return LiDARBoxes(self.tensor.to(device))
+        return LiDARBoxes(self.tensor.to(device), with_yaw=self.with_yaw)
 
 
 class DepthBoxes:

@@ -43,7 +43,10 @@ def nms_batched(kind, boxes, scores, offsets, thresh, pre_max=None, post_max=Non
     kind: 'rotate' (boxes [N, 5] xyxyr, IoU > thresh), 'normal' (axis-aligned IoU of the
     first four columns > thresh), 'circle' (boxes [N, >= 2] centres, squared distance <=
     thresh) or 'aligned3d' (boxes [N, 7]: x1, y1, z1, x2, y2, z2, class; a later box goes
-    unless 3-D IoU * same-class <= thresh, see aligned_3d_nms).  List s is rows offsets[s] .. offsets[s+1] of boxes / scores (offsets: int
+    unless 3-D IoU * same-class <= thresh, see aligned_3d_nms) or 'mmcv' (boxes [N, 4]: x1, y1,
+    x2, y2 already shifted by class * (max + 1) as mmcv's batched_nms does; mmcv.ops.nms's test
+    inter > thresh * (area_i + area_j - inter), no division and no floor on the union).
+    List s is rows offsets[s] .. offsets[s+1] of boxes / scores (offsets: int
     [S + 1] on the device).  thresh: a float, or one per list (sequence or tensor).
     pre_max: only the pre_max best boxes of a list take part; it also bounds the work, so
     it is required when N exceeds 16384 (a single list: its length is the bound).

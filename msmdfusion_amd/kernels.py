@@ -1788,6 +1788,7 @@ def boxes_iou_bev(boxes_a, boxes_b):
 
 NMS_KINDS = {"rotate": 0, "rotated": 0, "normal": 1, "circle": 2}
 NMS_ALIGNED3D = "aligned3d"      # its own entry point (msmd_nms_aligned3d_f32), not a kind code
+NMS_MMCV = "mmcv"                # likewise (msmd_nms_mmcv_f32): mmcv.ops.nms's pair test
 NMS_MAX_SEGMENT = 16384
 
 
@@ -1799,15 +1800,16 @@ def nms_segments(kind, boxes, offsets, thresh, max_segment, post_max=None, order
                  keep=None, num_keep=None, workspace=None):
     """Greedy NMS of every segment in one call (two launches, nothing read back).
     boxes [total, >= 5 | 4 | 2] float32 ('aligned3d': [total, >= 7] rows x1, y1, z1, x2, y2, z2,
-    class), each segment (rows offsets[s] .. offsets[s+1], int32
-    [S + 1] on the device) already in descending score order; only the first `max_segment`
+    class; 'mmcv': [total, >= 4] rows x1, y1, x2, y2 already shifted by class), each segment
+    (rows offsets[s] .. offsets[s+1], int32 [S + 1] on the device) already in descending score
+    order; only the first `max_segment`
     rows of a segment take part.  thresh: float32 [S] on the device.  order (optional, long
     [total]): the caller's sort permutation -- kept rows are then reported as order[row].
     -> (keep long [S, min(post_max, max_segment)], -1 past num_keep[s]; num_keep int32 [S]).
     keep / num_keep / workspace (uint8, nms_workspace_bytes) may be passed in: with all three
     the call allocates nothing."""
     _need_cuda(boxes, offsets, thresh, order, keep, num_keep, workspace)
-    code = None if kind == NMS_ALIGNED3D else NMS_KINDS[kind]
+    code = None if kind in (NMS_ALIGNED3D, NMS_MMCV) else NMS_KINDS[kind]
     if boxes.dtype != torch.float32 or boxes.dim() != 2 or not boxes.is_contiguous():
         raise ValueError("boxes must be a contiguous float32 [total, columns] tensor")
     if offsets.dtype != torch.int32 or thresh.dtype != torch.float32:
@@ -1836,6 +1838,12 @@ def nms_segments(kind, boxes, offsets, thresh, max_segment, post_max=None, order
     ws = _ws(nbytes, boxes.device) if workspace is None else workspace
     if ws.numel() * ws.element_size() < nbytes:
         raise ValueError("workspace holds %d bytes, %d needed" % (ws.numel(), nbytes))
+    if kind == NMS_MMCV:
+        check(lib.msmd_nms_mmcv_f32(_p(boxes), boxes.shape[1], _p(offsets.contiguous()), segments,
+                                    total, max_segment, _p(thresh.contiguous()), post, _p(order),
+                                    _p(keep), stride, _p(num_keep), _p(ws), nbytes, _stream()),
+              "msmd_nms_mmcv_f32")
+        return keep, num_keep
     if code is None:
         check(lib.msmd_nms_aligned3d_f32(_p(boxes), boxes.shape[1], _p(offsets.contiguous()),
                                          segments, total, max_segment, _p(thresh.contiguous()),
@@ -1948,6 +1956,68 @@ def points_in_boxes_count(boxes, pts):
     check(lib.msmd_points_in_boxes_count_f32(_p(boxes), _p(pts), pts.shape[2], b, t, m, _p(count),
                                              _stream()), "msmd_points_in_boxes_count_f32")
     return count
+
+
+# ------------------------------------------------ 3DSSD candidate targets (row n5)
+SSD3D_GT_CHUNK = lib.msmd_ssd3d_gt_chunk()
+SSD3D_TABLE_WIDTH = 33      # centre 3, half sizes 3, direction residual 1, sin / cos 2, corners 24
+SSD3D_TARGET_NAMES = ("vote_targets", "center_targets", "size_res_targets", "dir_class_targets",
+                      "dir_res_targets", "mask_targets", "centerness_targets", "corner3d_targets",
+                      "vote_mask", "positive_mask", "negative_mask")
+
+
+def ssd3d_targets(aggregated, seeds, gt_boxes, vote_boxes, labels, box_offsets, box_table,
+                  dir_class, num_classes, pos_distance_thr):
+    """SSD3DHead.get_targets_single for every sample in one launch (msmd_ssd3d_targets_f32).
+    aggregated float32 [B, N, 3]; seeds float32 [B, >= N, 3] (the first N of each sample are
+    read; a view with a sample stride is taken as it is); gt_boxes / vote_boxes float32 [T, 7] in
+    the points_in_boxes frame, labels long [T] (-1: the row does not exist), box_offsets int32
+    [B + 1] on the device; box_table float32 [T, 33] and dir_class long [T] as msmd_hip.h lays
+    them out.  -> the reference's eleven per-sample results stacked, in its order
+    (SSD3D_TARGET_NAMES); center_targets are absolute; the three masks are bool."""
+    _need_cuda(aggregated, seeds, gt_boxes, vote_boxes, labels, box_offsets, box_table, dir_class)
+    _need_dtype(aggregated, torch.float32, "aggregated")
+    _need_dtype(seeds, torch.float32, "seeds")
+    if aggregated.dim() != 3 or aggregated.shape[2] != 3 or not aggregated.is_contiguous():
+        raise ValueError("aggregated must be a contiguous float32 [B, N, 3] tensor, got %s"
+                         % (tuple(aggregated.shape),))
+    batch, n = aggregated.shape[:2]
+    if seeds.dim() != 3 or seeds.shape[0] != batch or seeds.shape[1] < n or seeds.shape[2] != 3:
+        raise ValueError("seeds must be [B, >= N, 3], got %s" % (tuple(seeds.shape),))
+    if seeds.numel() and (seeds.stride(2) != 1 or seeds.stride(1) != 3 or
+                          (batch > 1 and seeds.stride(0) < n * 3)):
+        seeds = seeds[:, :n].contiguous()
+    seed_stride = seeds.stride(0) if batch > 1 else max(seeds.shape[1], n) * 3
+    total = gt_boxes.shape[0]
+    for t, w, what in ((gt_boxes, 7, "gt_boxes"), (vote_boxes, 7, "vote_boxes"),
+                       (box_table, SSD3D_TABLE_WIDTH, "box_table")):
+        _need_dtype(t, torch.float32, what)
+        if t.dim() != 2 or tuple(t.shape) != (total, w) or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float32 [%d, %d] tensor, got %s"
+                             % (what, total, w, tuple(t.shape)))
+    for t, what in ((labels, "labels"), (dir_class, "dir_class")):
+        _need_dtype(t, torch.long, what)
+        if t.dim() != 1 or t.numel() != total or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous long [%d] tensor" % (what, total))
+    _need_dtype(box_offsets, torch.int32, "box_offsets")
+    if box_offsets.numel() != batch + 1:
+        raise ValueError("box_offsets holds B + 1 entries")
+    dev, classes = aggregated.device, int(num_classes)
+    f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)       # noqa: E731
+    l = lambda *shape: torch.empty(shape, dtype=torch.long, device=dev)          # noqa: E731,E741
+    u = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=dev)         # noqa: E731
+    vote, center, size = f(batch, n, 3), f(batch, n, 3), f(batch, n, 3)
+    dcls, dres, mask = l(batch, n), f(batch, n), l(batch, n)
+    cness, corners = f(batch, n, classes), f(batch, n, 8, 3)
+    vmask, pos, neg = u(batch, n), u(batch, n), u(batch, n)
+    check(lib.msmd_ssd3d_targets_f32(
+        _p(aggregated), _p(seeds), seed_stride, _p(gt_boxes), _p(vote_boxes), _p(labels),
+        _p(box_offsets.contiguous()), _p(box_table), SSD3D_TABLE_WIDTH, _p(dir_class), batch, n,
+        total, classes, float(pos_distance_thr), _p(vote), _p(center), _p(size), _p(dcls),
+        _p(dres), _p(mask), _p(cness), _p(corners), _p(vmask), _p(pos), _p(neg), _stream()),
+        "msmd_ssd3d_targets_f32")
+    return (vote, center, size, dcls, dres, mask, cness, corners, vmask.view(torch.bool),
+            pos.view(torch.bool), neg.view(torch.bool))
 
 
 # ------------------------------------------------ Anchor3DHead targets / loss (row n3)

@@ -121,16 +121,18 @@ def weight_reduce_loss(loss, weight=None, reduction="mean", avg_factor=None):
 
 
 class CrossEntropyLoss(nn.Module):
-    """mmdet CrossEntropyLoss in its softmax form, with class_weight and every reduction (the
-    VoteNet configs use reduction='sum' and, for objectness, class_weight=[0.2, 0.8]).
+    """mmdet CrossEntropyLoss, with class_weight and every reduction (the VoteNet configs use
+    reduction='sum' and, for objectness, class_weight=[0.2, 0.8]).  use_sigmoid=True (3DSSD's
+    centerness loss) is mmdet's binary_cross_entropy: binary_cross_entropy_with_logits on a
+    float target of the prediction's shape, then weight, reduction, loss_weight.
     anchor_head.py keeps its own mean-only form: it takes the weighted sum over ~10^5 anchors in
     float64, which these per-proposal sums do not need."""
 
     def __init__(self, use_sigmoid=False, use_mask=False, reduction="mean", class_weight=None,
                  loss_weight=1.0):
         super().__init__()
-        if use_sigmoid or use_mask:
-            raise NotImplementedError("CrossEntropyLoss: the softmax form only")
+        if use_mask:
+            raise NotImplementedError("CrossEntropyLoss: the mask form is not built")
         self.use_sigmoid, self.use_mask = use_sigmoid, use_mask
         self.reduction, self.loss_weight, self.class_weight = reduction, loss_weight, class_weight
 
@@ -140,9 +142,18 @@ class CrossEntropyLoss(nn.Module):
         reduction = reduction_override if reduction_override else self.reduction
         class_weight = None if self.class_weight is None else \
             cls_score.new_tensor(self.class_weight)
-        loss = F.cross_entropy(cls_score, label, weight=class_weight, reduction="none")
         if weight is not None:
             weight = weight.float()
+        if self.use_sigmoid:
+            # mmdet binary_cross_entropy (cross_entropy_loss.py): its label expansion serves class
+            # indices; 3DSSD passes a target of the prediction's shape, which goes through as is
+            if cls_score.dim() != label.dim():
+                raise NotImplementedError("CrossEntropyLoss(use_sigmoid=True): the target must "
+                                          "have the prediction's shape")
+            loss = F.binary_cross_entropy_with_logits(cls_score, label.float(),
+                                                      pos_weight=class_weight, reduction="none")
+        else:
+            loss = F.cross_entropy(cls_score, label, weight=class_weight, reduction="none")
         return self.loss_weight * weight_reduce_loss(loss, weight, reduction, avg_factor)
 
 

@@ -167,7 +167,58 @@ class PartialBinBasedBBoxCoder:
         return angle
 
 
-_BBOX_CODERS = {"PartialBinBasedBBoxCoder": PartialBinBasedBBoxCoder}
+class AnchorFreeBBoxCoder(PartialBinBasedBBoxCoder):
+    """anchor_free_bbox_coder.py (3DSSD): no size classes -- the size target is the half size,
+    the direction residual is normalised by the bin width."""
+
+    def __init__(self, num_dir_bins, with_rot=True):
+        super().__init__(num_dir_bins, 0, [], with_rot=with_rot)
+
+    def encode(self, gt_bboxes_3d, gt_labels_3d):
+        """:23-51 -- (gravity centre, half sizes, direction class, normalised residual).
+        Element-wise, so one call serves the concatenated boxes of a batch."""
+        center_target = gt_bboxes_3d.gravity_center
+        size_res_target = gt_bboxes_3d.dims / 2
+        box_num = gt_labels_3d.shape[0]
+        if self.with_rot:
+            dir_class_target, dir_res_target = self.angle2class(gt_bboxes_3d.yaw)
+            dir_res_target /= (2 * np.pi / self.num_dir_bins)
+        else:
+            dir_class_target = gt_labels_3d.new_zeros(box_num)
+            dir_res_target = gt_bboxes_3d.tensor.new_zeros(box_num)
+        return center_target, size_res_target, dir_class_target, dir_res_target
+
+    def decode(self, bbox_out):
+        """:53-85 -- predictions -> [batch, n, 7] (centre, size, angle)."""
+        center = bbox_out["center"]
+        batch_size, num_proposal = center.shape[:2]
+        if self.with_rot:
+            dir_class = torch.argmax(bbox_out["dir_class"], -1)
+            dir_res = torch.gather(bbox_out["dir_res"], 2, dir_class.unsqueeze(-1))
+            dir_res = dir_res.squeeze(2)
+            dir_angle = self.class2angle(dir_class, dir_res).reshape(batch_size, num_proposal, 1)
+        else:
+            dir_angle = center.new_zeros(batch_size, num_proposal, 1)
+        bbox_size = torch.clamp(bbox_out["size"] * 2, min=0.1)
+        return torch.cat([center, bbox_size, dir_angle], dim=-1)
+
+    def split_pred(self, cls_preds, reg_preds, base_xyz):
+        """:87-129 -- the head's two maps [B, C, P] -> the prediction dict."""
+        results = {"obj_scores": cls_preds}
+        reg_preds_trans = reg_preds.transpose(2, 1)
+        bins = self.num_dir_bins
+        results["center_offset"] = reg_preds_trans[..., 0:3]
+        results["center"] = base_xyz.detach() + reg_preds_trans[..., 0:3]
+        results["size"] = reg_preds_trans[..., 3:6]
+        results["dir_class"] = reg_preds_trans[..., 6:6 + bins]
+        dir_res_norm = reg_preds_trans[..., 6 + bins:6 + 2 * bins]
+        results["dir_res_norm"] = dir_res_norm
+        results["dir_res"] = dir_res_norm * (2 * np.pi / bins)
+        return results
+
+
+_BBOX_CODERS = {"PartialBinBasedBBoxCoder": PartialBinBasedBBoxCoder,
+                "AnchorFreeBBoxCoder": AnchorFreeBBoxCoder}
 
 
 def build_bbox_coder(cfg):
