@@ -7,62 +7,14 @@ import pytest
 import torch
 
 from msmdfusion_amd import kernels as K
-from msmdfusion_amd import synthetic as S
-from oracle import oracle as O
+from point_search_cases import (FPS_NUM, GRID, MAX_CLUSTER, RADIUS, THRESH, cloud, oracle_batch,
+                                oracle_fps_nn, with_batch)
 
 pytestmark = pytest.mark.gpu
-
-GRID = [41, 120, 120]
-FPS_NUM, RADIUS, MAX_CLUSTER, THRESH = 64, 6, 8, 13.3
 
 
 def _np(t):
     return t.detach().cpu().numpy()
-
-
-def _oracle_fps_nn(query, key, fps_num, radius, max_cluster, thresh, parts=None):
-    """fps_NN_fast (:276-323) with oracle pieces, as tests/test_gpu_fusion.py composes it."""
-    nq = query.shape[0]
-    if nq <= fps_num:
-        return O.nn_search(query[:, 1:], key[:, 1:], thresh)
-    q = query[:, 1:].astype(np.float32)[None]
-    rep_idx = O.furthest_point_sample(q, fps_num)[0]
-    rep = query[rep_idx, 1:]
-    rep_nn = O.nn_search(rep, key[:, 1:], thresh)
-    grp = O.ball_query(0, radius, max_cluster, q, rep.astype(np.float32)[None])[0]
-    if parts is not None:
-        parts.update(rep_nn=rep_nn, grp=grp)
-    return O.nn_assign(grp, rep_nn, nq)
-
-
-def oracle_batch(q, k, batch, fps_num=FPS_NUM, radius=RADIUS, max_cluster=MAX_CLUSTER,
-                 thresh=THRESH, quirks=False, n_pad=0):
-    """The per-sample loop of grouped_sparse_conv (:349-369): cumulative bases, or the
-    reference's own (the previous sample's count) with quirks."""
-    out = np.full((q.shape[0] + n_pad,), -1, np.int64)
-    c3 = [int((k[:, 0] == b).sum()) for b in range(batch)]
-    o3 = np.cumsum([0] + c3)
-    for b in range(batch):
-        rows = np.flatnonzero(q[:, 0] == b)
-        kb = k[k[:, 0] == b]
-        if rows.size == 0 or kb.shape[0] == 0:
-            continue
-        nn = _oracle_fps_nn(q[rows], kb, fps_num, radius, max_cluster, thresh).astype(np.int64)
-        base = (c3[b - 1] if b else 0) if quirks else o3[b]
-        out[rows] = np.where(nn >= 0, nn + base, nn)
-    return out
-
-
-def with_batch(zyx, b):
-    zyx = np.asarray(zyx, np.int32).reshape(-1, 3)
-    return np.concatenate([np.full((zyx.shape[0], 1), b, np.int32), zyx], 1)
-
-
-def cloud(n, b, seed, extent=GRID, clustered=True):
-    rows = S.random_voxel_indices(n, 1, extent, seed=seed, clustered=clustered)
-    assert rows.shape[0] == n
-    rows[:, 0] = b
-    return rows
 
 
 @pytest.fixture(scope="module")
@@ -108,7 +60,7 @@ def test_ragged_batch_with_every_mode(enc, dev, calls):
     q, k = ragged_batch()
     exp = oracle_batch(q, k, 4)
     parts = {}
-    a = _oracle_fps_nn(q[q[:, 0] == 0], k[k[:, 0] == 0], FPS_NUM, RADIUS, MAX_CLUSTER, THRESH, parts)
+    a = oracle_fps_nn(q[q[:, 0] == 0], k[k[:, 0] == 0], FPS_NUM, RADIUS, MAX_CLUSTER, THRESH, parts)
     assert (a >= 0).any() and (a < 0).any(), "sample (a) needs valid and unassigned rows"
     assert (parts["rep_nn"] < 0).any() and (parts["rep_nn"] >= 0).any(), "needs a dead representative"
     # the first-nsample cap binds: some ball holds more points than it may keep
