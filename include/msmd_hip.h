@@ -499,8 +499,10 @@ int msmd_spconv_fwd_split(const float* in_feat /* [n_in,c_in] */, int n_in, int 
                           msmd_stream_t stream);
 
 /* The same call that also leaves, per row tile of the output (128 or 256 rows:
- * msmd_spconv_fwd_split_tile_rows(c_out)), the column sums and sums of squares of the rows
- * it wrote: bn_partials[msmd_spconv_fwd_split_stats_blocks(n_out, c_out)][2][c_out] -- the statistics
+ * msmd_spconv_fwd_split_tile_rows(c_out)), the pivoted column statistics of the rows it
+ * wrote: bn_partials[msmd_spconv_fwd_split_stats_blocks(n_out, c_out)][3][c_out] = per channel a
+ * pivot K (the tile's first row), sum (x - K) and sum (x - K)^2 over the tile's rows (raw
+ * float32 sums of x and x^2 cancel for a channel far from zero) -- the statistics
  * pass of the BatchNorm1d that follows a conv in make_sparse_convmodule / SparseBasicBlock
  * (mmdet3d/ops/sparse_block.py:87-117,161-190) without reading the output again
  * (msmd_bn_act_fwd_from_partials_f32 takes them).  bn_partials = NULL: msmd_spconv_fwd_split. */
@@ -681,19 +683,27 @@ int msmd_bn_act_fwd_f32(const float* x /* [n,c] */, const float* residual /* or 
                         size_t workspace_bytes, msmd_stream_t stream);
 
 /* Training-mode forward whose statistics pass was done by the producer of x:
- * partials[n_partials][2][c] = column sums / sums of squares of disjoint row blocks covering x
- * (msmd_spconv_fwd_split_stats).  Same outputs and running-stat update as msmd_bn_act_fwd_f32. */
+ * partials[n_partials][3][c] = per block of rows_per_partial consecutive rows (the last block the
+ * rest; n_partials = ceil(n / rows_per_partial), anything else is MSMD_ERR_INVALID_ARG) and per
+ * channel a pivot K (any value near the block's, e.g. its first row), sum (x - K), sum (x - K)^2
+ * (msmd_spconv_fwd_split_stats; there the blocks are the row tiles in tile order).  Same outputs
+ * and running-stat update as msmd_bn_act_fwd_f32. */
 int msmd_bn_act_fwd_from_partials_f32(const float* x, const float* residual, int n, int c,
                                       const float* gamma, const float* beta,
                                       float* running_mean, float* running_var, float momentum,
                                       float eps, int relu, float* y, float* save_mean,
                                       float* save_invstd, const float* partials, int n_partials,
-                                      msmd_stream_t stream);
+                                      int rows_per_partial, msmd_stream_t stream);
 
 int msmd_bn_act_bwd_f32(const float* x, const float* y /* fwd output, for the ReLU mask */,
                         const float* dy, int n, int c, const float* gamma,
                         const float* save_mean, const float* save_invstd,
-                        int training, int relu, float* dx,
+                        int training,
+                        float eps /* the forward's; training != 0 and eps > 0: the pass, which
+                                     reads x anyway, takes the batch mean and variance again in
+                                     fp64 instead of working from the float32 roundings in
+                                     save_mean / save_invstd; <= 0: from those */,
+                        int relu, float* dx,
                         float* dresidual /* or NULL */, float* dgamma, float* dbeta,
                         void* workspace, size_t workspace_bytes, msmd_stream_t stream);
 /* BatchNorm + ReLU WITHOUT a residual, backward without y: the ReLU mask is recomputed from x
@@ -701,8 +711,9 @@ int msmd_bn_act_bwd_f32(const float* x, const float* y /* fwd output, for the Re
  * read one array less each.  Results = msmd_bn_act_bwd_f32(relu = 1) given the forward's y. */
 int msmd_bn_relu_bwd_f32(const float* x, const float* dy, int n, int c, const float* gamma,
                          const float* beta, const float* save_mean, const float* save_invstd,
-                         int training, float* dx, float* dgamma, float* dbeta,
-                         void* workspace, size_t workspace_bytes, msmd_stream_t stream);
+                         int training, float eps /* as above */, float* dx, float* dgamma,
+                         float* dbeta, void* workspace, size_t workspace_bytes,
+                         msmd_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
  * a6p  Sparse max-pool (SparseMaxPool3d), fp32, any channel count

@@ -124,9 +124,9 @@ SIGNATURES = {
     "msmd_bn_workspace_bytes": (_sz, [_i, _i]),
     "msmd_bn_act_fwd_f32": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "msmd_bn_act_fwd_from_partials_f32": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _vp,
-                                               _vp, _vp, _vp, _i, _vp]),
-    "msmd_bn_act_bwd_f32": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "msmd_bn_relu_bwd_f32": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+                                               _vp, _vp, _vp, _i, _i, _vp]),
+    "msmd_bn_act_bwd_f32": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "msmd_bn_relu_bwd_f32": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "msmd_dense_scatter_f32": (_i, [_vp, _vp, _i, _i, _i, _ip, _vp, _vp]),
     "msmd_dense_gather_f32": (_i, [_vp, _vp, _i, _i, _i, _ip, _vp, _vp]),
     "msmd_bev_scatter_nhwc_f32": (_i, [_vp, _vp, _i, _i, _i, _ip, _vp, _i, _i, _vp]),

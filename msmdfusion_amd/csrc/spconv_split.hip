@@ -974,25 +974,33 @@ __global__ __launch_bounds__(WV * 64, WV == 4 ? 2 : 1) void spconv_fwd_split_ker
           }
         }
       }
-      // The BatchNorm that follows wants the per-channel sum and sum of squares of these
-      // rows: the tile's partials come straight from the accumulators (bn.hip's statistics
-      // pass would read the whole output again) -- one [2][c_out] slot per row tile, rows and
-      // waves in fixed order: deterministic.  The four waves' sums meet in the weight buffer,
-      // which is idle between a tile's last unit and the next tile's first (a barrier makes
-      // sure every wave has left that unit); LDS of its own for this -- 4 KB -- took the NT = 8
-      // instantiation from two workgroups per CU to one (145 -> 185 us per launch), and one
-      // slot per WAVE instead made the BN's finalize kernel read four times as many (7 -> 12 us).
+      // The BatchNorm that follows wants the per-channel mean and variance of these rows: the
+      // tile's partials come straight from the accumulators (bn.hip's statistics pass would
+      // read the whole output again) -- one [3][c_out] slot per row tile, rows and waves in
+      // fixed order: deterministic.  Raw float32 sums of x and x * x lose the variance of a
+      // channel that sits many standard deviations from zero, so each wave sums x - K and
+      // (x - K)^2 about a pivot K = its own first row (a shuffle away: lane (0, q) of r = 0),
+      // and the slot carries [K][sum (x - K)][sum (x - K)^2] about wave 0's pivot, the tile's
+      // first row: the other waves' sums are moved there (d = K_w - K_0: s_w + n_w d,
+      // ss_w + 2 d s_w + n_w d^2; every term of the order of the channel's spread).  The waves'
+      // sums meet in the weight buffer, which is idle between a tile's last unit and the next
+      // tile's first (a barrier makes sure every wave has left that unit); LDS of its own for
+      // this -- 4 KB -- took the NT = 8 instantiation from two workgroups per CU to one
+      // (145 -> 185 us per launch), and one slot per WAVE instead made the BN's finalize kernel
+      // read four times as many (7 -> 12 us).
       if (bn_part) {
         float* stat = (float*)wl;
-        float* st_w = stat + wave * (2 * NT * 16);
+        float* st_w = stat + wave * (3 * NT * 16);
         __builtin_amdgcn_s_barrier();          // nobody reads weights from wl any more
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
-          f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
+          f32x4 kp, s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) kp[e] = __shfl(acc[0][n][e], lane & 48, 64);
 #pragma unroll
           for (int r = 0; r < R; ++r) {
             const bool ok = rt * kRows + lr[r] < n_out;
-            const f32x4 v = ok ? acc[r][n] : (f32x4){0.f, 0.f, 0.f, 0.f};
+            const f32x4 v = ok ? acc[r][n] - kp : (f32x4){0.f, 0.f, 0.f, 0.f};
             s1 += v;
             s2 += v * v;
           }
@@ -1004,18 +1012,33 @@ __global__ __launch_bounds__(WV * 64, WV == 4 ? 2 : 1) void spconv_fwd_split_ker
               s2[e] += __shfl_xor(s2[e], m, 64);
             }
           if (j == 0) {
-            *(f32x4*)(st_w + 16 * n + 4 * q) = s1;
-            *(f32x4*)(st_w + NT * 16 + 16 * n + 4 * q) = s2;
+            *(f32x4*)(st_w + 16 * n + 4 * q) = kp;
+            *(f32x4*)(st_w + NT * 16 + 16 * n + 4 * q) = s1;
+            *(f32x4*)(st_w + 2 * NT * 16 + 16 * n + 4 * q) = s2;
           }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        if (tid < 2 * NT * 16) {
-          float v = 0.f;
+        if (tid < NT * 16) {
+          const int left = n_out - rt * kRows;   // rows of this tile that exist (wave w: 32 w ..)
+          const float k0 = stat[tid];
+          float su = stat[NT * 16 + tid], sq = stat[2 * NT * 16 + tid];
 #pragma unroll
-          for (int w2 = 0; w2 < WV; ++w2) v += stat[w2 * (2 * NT * 16) + tid];
-          const int which = tid >= NT * 16 ? 1 : 0, c = tid - which * NT * 16;
-          if (c < cout) bn_part[(size_t)rt * 2 * ldo + (size_t)which * ldo + 16 * mt0 + c] = v;
+          for (int w2 = 1; w2 < WV; ++w2) {
+            const float* sw = stat + w2 * (3 * NT * 16) + tid;
+            const int have = left - 32 * w2;
+            if (have > 0) {     // (a wave past the end holds no row: its pivot means nothing)
+              const float nw = (float)(have < 32 ? have : 32), d = sw[0] - k0, u = sw[NT * 16];
+              su += u + nw * d;
+              sq += sw[2 * NT * 16] + 2.f * d * u + nw * d * d;
+            }
+          }
+          if (tid < cout) {
+            float* o = bn_part + (size_t)rt * 3 * ldo + 16 * mt0 + tid;
+            o[0] = k0;
+            o[ldo] = su;
+            o[2 * (size_t)ldo] = sq;
+          }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();          // (before the next tile's weights land there)
@@ -1569,9 +1592,10 @@ MSMD_EXPORT size_t msmd_spconv_fwd_split_workspace_bytes(int n_out, int cout) {
   return fwd_sk_ws_bytes(n_out, kMaxK, cout);
 }
 
-// bn_partials (or NULL): [msmd_spconv_fwd_split_stats_blocks(n_out, c_out)][2][c_out] floats
-// (one block per row tile of this width's kernel: 128 or 256 rows) -- per row tile the column sums
-// and sums of squares of the rows written (what msmd_bn_act_fwd_from_partials_f32 takes)
+// bn_partials (or NULL): [msmd_spconv_fwd_split_stats_blocks(n_out, c_out)][3][c_out] floats
+// (one block per row tile of this width's kernel: 128 or 256 rows) -- per row tile a pivot K (the
+// tile's first row) and the column sums of x - K and (x - K)^2 over the rows written (what
+// msmd_bn_act_fwd_from_partials_f32 takes)
 MSMD_EXPORT int msmd_spconv_fwd_split_stats_blocks(int n_out, int cout) {
   return ceil_div(n_out > 0 ? n_out : 0, 32 * fwd_waves(cout));
 }

@@ -1370,11 +1370,12 @@ def conv_forward_split(feat, packed_weight, nbr, n_out, c_out, planes=3, weight_
         if tile_prefix.numel() != (int(n_out) + rows - 1) // rows + 1:
             raise ValueError("tile_prefix was not computed for %d-row tiles (K.tile_prefix(nbr, "
                              "K.split_tile_rows(c_out)))" % rows)
-    # bn_stats: also the per-tile column sums / sums of squares of the output, for the
-    # BatchNorm that follows (bn_act_forward(partials=...)) -> (out, partials)
+    # bn_stats: also the per-tile pivoted column statistics of the output ([tiles, 3, c_out]:
+    # pivot, sum (x - pivot), sum (x - pivot)^2), for the BatchNorm that follows
+    # (bn_act_forward(partials=...)) -> (out, partials)
     part = None
     if bn_stats and int(n_out) > 0:
-        part = torch.empty((int(lib.msmd_spconv_fwd_split_stats_blocks(int(n_out), int(c_out))), 2,
+        part = torch.empty((int(lib.msmd_spconv_fwd_split_stats_blocks(int(n_out), int(c_out))), 3,
                             int(c_out)), dtype=torch.float32, device=f.device)
     _launch("spconv_fwd_split", lambda: check(
         lib.msmd_spconv_fwd_split_stats(_p(f), n_in, c_in, _p(packed_weight), _p(nbr), ld,
@@ -1474,9 +1475,9 @@ def conv_wgrad_split(feat, d_out, pairs, num, planes=3, krsc_shape=None, segment
 # ------------------------------------------------------------------ BN (+residual)(+ReLU)
 def bn_act_forward(x, residual, gamma, beta, running_mean, running_var, training, momentum, eps,
                    relu, partials=None):
-    """-> (y, save_mean, save_invstd).  partials (training only): [blocks, 2, c] column sums /
-    sums of squares of disjoint row blocks covering x, from the kernel that produced x
-    (conv_forward_split(bn_stats=True)): the statistics pass is skipped."""
+    """-> (y, save_mean, save_invstd).  partials (training only): [blocks, 3, c] pivot /
+    sum (x - pivot) / sum (x - pivot)^2 per block of split_tile_rows(c) rows of x, from the
+    kernel that produced x (conv_forward_split(bn_stats=True)): the statistics pass is skipped."""
     _need_cuda(x, gamma, beta)
     xx = x.contiguous().float()
     n, c = xx.shape
@@ -1488,12 +1489,13 @@ def bn_act_forward(x, residual, gamma, beta, running_mean, running_var, training
     ws = _ws(nbytes, dev)
     res = None if residual is None else residual.contiguous().float()
     if partials is not None and training:
-        assert partials.shape[1:] == (2, c) and partials.is_contiguous()
+        assert partials.shape[1:] == (3, c) and partials.is_contiguous()
     if partials is not None and training and n > 0:
         check(lib.msmd_bn_act_fwd_from_partials_f32(
             _p(xx), _p(res), n, c, _p(gamma), _p(beta), _p(running_mean), _p(running_var),
             float(momentum), float(eps), int(bool(relu)), _p(y), _p(mean), _p(invstd),
-            _p(partials), int(partials.shape[0]), _stream()), "msmd_bn_act_fwd_from_partials_f32")
+            _p(partials), int(partials.shape[0]), split_tile_rows(c), _stream()),
+            "msmd_bn_act_fwd_from_partials_f32")
         return y, mean, invstd
     check(lib.msmd_bn_act_fwd_f32(_p(xx), _p(res), n, c, _p(gamma), _p(beta), _p(running_mean),
                                   _p(running_var), int(bool(training)), float(momentum),
@@ -1502,8 +1504,11 @@ def bn_act_forward(x, residual, gamma, beta, running_mean, running_var, training
     return y, mean, invstd
 
 
-def bn_act_backward(x, y, dy, gamma, save_mean, save_invstd, training, relu, want_residual):
-    """-> (dx, dresidual | None, dgamma, dbeta)"""
+def bn_act_backward(x, y, dy, gamma, save_mean, save_invstd, training, relu, want_residual,
+                    eps=0.0):
+    """-> (dx, dresidual | None, dgamma, dbeta).  eps: the forward's -- in training mode the
+    pass then takes the batch statistics again in fp64 instead of working from the float32
+    save_mean / save_invstd (0: from those)."""
     _need_cuda(x, dy)
     xx, g = x.contiguous().float(), dy.contiguous().float()
     n, c = xx.shape
@@ -1515,13 +1520,14 @@ def bn_act_backward(x, y, dy, gamma, save_mean, save_invstd, training, relu, wan
     nbytes = lib.msmd_bn_workspace_bytes(n, c)
     ws = _ws(nbytes, dev)
     check(lib.msmd_bn_act_bwd_f32(_p(xx), _p(y), _p(g), n, c, _p(gamma), _p(save_mean),
-                                  _p(save_invstd), int(bool(training)), int(bool(relu)), _p(dx),
+                                  _p(save_invstd), int(bool(training)), float(eps),
+                                  int(bool(relu)), _p(dx),
                                   _p(dres), _p(dgamma), _p(dbeta), _p(ws), nbytes, _stream()),
           "msmd_bn_act_bwd_f32")
     return dx, dres, dgamma, dbeta
 
 
-def bn_relu_backward(x, dy, gamma, beta, save_mean, save_invstd, training):
+def bn_relu_backward(x, dy, gamma, beta, save_mean, save_invstd, training, eps=0.0):
     """bn_act_backward for BatchNorm + ReLU without a residual, without reading y (the mask is
     recomputed from x: csrc/bn.hip BwdStatRecompute).  -> (dx, dgamma, dbeta)"""
     _need_cuda(x, dy)
@@ -1533,7 +1539,8 @@ def bn_relu_backward(x, dy, gamma, beta, save_mean, save_invstd, training):
     nbytes = lib.msmd_bn_workspace_bytes(n, c)
     ws = _ws(nbytes, dev)
     check(lib.msmd_bn_relu_bwd_f32(_p(xx), _p(g), n, c, _p(gamma), _p(beta), _p(save_mean),
-                                   _p(save_invstd), int(bool(training)), _p(dx), _p(dgb[0]),
+                                   _p(save_invstd), int(bool(training)), float(eps), _p(dx),
+                                   _p(dgb[0]),
                                    _p(dgb[1]), _p(ws), nbytes, _stream()), "msmd_bn_relu_bwd_f32")
     return dx, dgb[0], dgb[1]
 

@@ -279,8 +279,8 @@ class _SparseConvFunction(Function):
 def sparse_conv(features, weight, rb, krsc=False, bn_stats=None):
     """weight: [K,Cin,Cout], or the KRSC module parameter with krsc=True (read
     and differentiated in place -- no permute/contiguous copies per step).
-    bn_stats: a one-slot list that receives the output's BatchNorm partials (per-tile column
-    sums / sums of squares, or None where the kernel in use does not produce them) for
+    bn_stats: a one-slot list that receives the output's BatchNorm partials (per-tile pivot and
+    column sums about it, or None where the kernel in use does not produce them) for
     bn_act(..., stats=...)."""
     if not (torch.is_grad_enabled() and (features.requires_grad or weight.requires_grad)):
         if bn_stats is not None:
@@ -300,19 +300,20 @@ class _BNActFunction(Function):
         y, mean, invstd = K.bn_act_forward(x, residual, gamma, beta, running_mean, running_var,
                                            training, momentum, eps, relu, partials=stats)
         ctx.save_for_backward(x, y, gamma, beta, mean, invstd)
-        ctx.cfg = (bool(training), bool(relu), residual is not None)
+        ctx.cfg = (bool(training), bool(relu), residual is not None, float(eps))
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, y, gamma, beta, mean, invstd = ctx.saved_tensors
-        training, relu, has_res = ctx.cfg
+        training, relu, has_res, eps = ctx.cfg
         if relu and not has_res and gamma.dtype == torch.float32 and beta.dtype == torch.float32:
             # BN + ReLU: the mask comes from x (bit-identical decision), y is not read
-            dx, dgamma, dbeta = K.bn_relu_backward(x, dy, gamma, beta, mean, invstd, training)
+            dx, dgamma, dbeta = K.bn_relu_backward(x, dy, gamma, beta, mean, invstd, training,
+                                                   eps)
             return dx, None, dgamma, dbeta, None, None, None, None, None, None, None
         dx, dres, dgamma, dbeta = K.bn_act_backward(x, y, dy, gamma, mean, invstd, training, relu,
-                                                    has_res and ctx.needs_input_grad[1])
+                                                    has_res and ctx.needs_input_grad[1], eps)
         return dx, dres, dgamma, dbeta, None, None, None, None, None, None, None
 
 
@@ -378,13 +379,15 @@ def bn_act(x, bn, relu=False, residual=None, stats=None):
     """Apply an nn.BatchNorm1d module (its parameters / buffers / mode) fused
     with an optional residual add and ReLU.  Same semantics as
     relu(bn(x) + residual), including the running-stat update.
-    stats: x's per-block column sums / sums of squares when the kernel that produced x left
+    stats: x's per-tile pivoted column statistics when the kernel that produced x left
     them (sparse_conv(bn_stats=[None]) -> the list's entry): the statistics pass over x is
     skipped in training mode."""
     if x.shape[0] == 0:     # SparseSequential skips dense modules on empty tensors
         return x
-    fusable = (x.is_cuda and x.dtype == torch.float32 and x.shape[1] % 4 == 0 and bn.affine
-               and bn.momentum is not None)
+    # (the kernels own a float4 channel group per thread of a 256-thread block: c % 4 == 0,
+    # c <= 1024)
+    fusable = (x.is_cuda and x.dtype == torch.float32 and x.shape[1] % 4 == 0
+               and x.shape[1] <= 1024 and bn.affine and bn.momentum is not None)
     if not fusable:
         y = bn(x)
         if residual is not None:

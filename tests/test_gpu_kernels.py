@@ -503,10 +503,11 @@ def test_rulebook_plan_many_equals_the_single_plans(dev):
                                       (96, 176), (128, 160)])
 def test_conv_epilogue_leaves_the_batchnorm_partials(dev, cin, cout):
     """msmd_spconv_fwd_split_stats: per row tile (128 rows, 256 in the ping-pong form from 161
-    output channels up) the column sums and sums of squares of the rows the conv wrote (every
-    instantiation width: 2 / 4 / 6 / 8 / 12 column tiles, a partial last
-    channel tile, a partial last row tile; stream-K pieces summed by the owner first), and
-    msmd_bn_act_fwd_from_partials_f32 == the BatchNorm with its own statistics pass."""
+    output channels up) a pivot K (the tile's first row) and the column sums of x - K and
+    (x - K)^2 of the rows the conv wrote (every instantiation width: 2 / 4 / 6 / 8 / 12 column
+    tiles, a partial last channel tile, a partial last row tile; stream-K pieces summed by the
+    owner first), and msmd_bn_act_fwd_from_partials_f32 == the BatchNorm with its own statistics
+    pass."""
     from msmdfusion_amd import kernels as K
     shape = [11, 64, 64]
     idx = S.random_voxel_indices(2100, 2, shape, seed=cin + cout)
@@ -523,15 +524,19 @@ def test_conv_epilogue_leaves_the_batchnorm_partials(dev, cin, cout):
                                          tile_prefix=pre, bn_stats=True)
         assert torch.equal(out, K.conv_forward_split(f, ws, plan["tiled"], n, cout, 3,
                                                      row_order=plan["order"], tile_prefix=pre))
-        assert part.shape == ((n + tr - 1) // tr, 2, cout)
+        assert part.shape == ((n + tr - 1) // tr, 3, cout)
         rows = out[plan["order"].long()].double()          # tile t = positions tr * t ..
         for ti in (0, part.shape[0] // 2, part.shape[0] - 1):
             blk = rows[tr * ti:tr * ti + tr]
             scale = max(blk.abs().max().item(), 1.0)
-            assert (part[ti, 0].double() - blk.sum(0)).abs().max().item() <= 1e-4 * scale
-            assert (part[ti, 1].double() - (blk * blk).sum(0)).abs().max().item() <= 1e-4 * scale ** 2
-        tot = part.double().sum(0)
-        assert (tot[0] - rows.sum(0)).abs().max().item() <= 1e-3
+            assert torch.equal(part[ti, 0].double(), blk[0])          # the pivot: the first row
+            dev_ = blk - blk[0]
+            assert (part[ti, 1].double() - dev_.sum(0)).abs().max().item() <= 1e-4 * scale
+            assert (part[ti, 2].double() - (dev_ * dev_).sum(0)).abs().max().item() <= 1e-4 * scale ** 2
+        cnt = torch.full((part.shape[0], 1), float(tr), device=dev, dtype=torch.float64)
+        cnt[-1] = n - tr * (part.shape[0] - 1)
+        tot = (part[:, 1].double() + cnt * part[:, 0].double()).sum(0)
+        assert (tot - rows.sum(0)).abs().max().item() <= 1e-3
     if cout % 4 == 0:
         bn = torch.nn.BatchNorm1d(cout).to(dev).train()
         bn2 = torch.nn.BatchNorm1d(cout).to(dev).train()
