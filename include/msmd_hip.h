@@ -1518,6 +1518,70 @@ int msmd_nms_mmcv_f32(const float* boxes /* [total_boxes, ld >= 4] */, int ld,
                       int32_t* num_keep /* [num_segments] */, void* workspace,
                       size_t workspace_bytes, msmd_stream_t stream);
 
+/* ---- FreeAnchor3DHead (COVERAGE n6, csrc/free_anchor.hip) -----------------------------------
+ * The training loss of mmdet3d/models/dense_heads/free_anchor3d_head.py:72-242 without its two
+ * [num_gt, num_anchors] IoU matrices per sample.  Boxes are nearest-BEV boxes (x1, y1, x2, y2)
+ * and the IoU is msmd_anchor_assign_f32's.  No [G, A] array exists in global memory, nothing is
+ * read back, there are no float atomics: every result is bitwise reproducible. */
+/* replaces: DeltaXYZWLHRBBoxCoder.decode (mmdet3d/core/bbox/coders/delta_xyzwhlr_bbox_coder.py:
+ * 56-91) followed by LiDARInstance3DBoxes.nearest_bev (core/bbox/structures/lidar_box3d.py:93-111)
+ * as free_anchor3d_head.py:112-116 applies them to every anchor of every sample.  Row r of
+ * deltas uses anchor r % num_anchors; only x, y, w, l and the rotation are decoded.
+ * code_size < 7 is refused (MSMD_ERR_INVALID_ARG). */
+int msmd_decode_nearest_bev_f32(const float* anchors /* [num_anchors,code_size] */,
+                                int num_anchors, int code_size,
+                                const float* deltas /* [batch*num_anchors,code_size] */,
+                                int batch, float* pred_bev /* [batch*num_anchors,4] */,
+                                msmd_stream_t stream);
+/* replaces: free_anchor3d_head.py:115-161 (the [G, A] IoU matrix of ground truths x decoded
+ * predictions, its row maximum, and sparse_coo_tensor / sparse.sum / nonzero per sample).
+ * Sample b owns prediction rows b * num_anchors .. and ground truths gt_offsets[b] ..
+ * gt_offsets[b+1] (a DEVICE array).  With t1 = bbox_thr and t2[i] = max over the sample's
+ * anchors of IoU(gt i, pred j):
+ *   box_prob[j, c] = max over the sample's i with gt_labels[i] == c of
+ *                    clamp((IoU(i, j) - t1) / (max(t2[i], t1) - t1), 0, 1), else 0,
+ * float32 with a true division.  A ground truth with t2 <= t1 contributes nothing (the
+ * reference gives 0 there as well, except NaN where an IoU equals t1 bit for bit).  A pair with
+ * a NaN coordinate in either box has a NaN IoU (tested explicitly: fmaxf / fminf would drop the
+ * NaN): it contributes nothing and stays out of t2, so a NaN prediction keeps a zero row and a
+ * NaN ground truth is ignored (the reference's row maximum would make t2 NaN instead).  A label
+ * outside [0, num_classes) is skipped.  Every row is written. */
+size_t msmd_free_anchor_box_prob_workspace_bytes(int num_gt);
+int msmd_free_anchor_box_prob_f32(const float* pred_bev /* [batch*num_anchors,4] */, int batch,
+                                  int num_anchors, const float* gt_bev /* [num_gt,4] */,
+                                  const int64_t* gt_labels /* [num_gt] */, int num_gt,
+                                  const int32_t* gt_offsets /* [batch+1] */, int num_classes,
+                                  float bbox_thr, float* box_prob /* [batch*num_anchors,C] */,
+                                  void* workspace, size_t workspace_bytes, msmd_stream_t stream);
+/* replaces: free_anchor3d_head.py:167-173 (the [G, A] matrix of ground truths x anchors and
+ * torch.topk over each row), for all ground truths of a batch at once: the anchors are shared by
+ * the samples.  Row i of matched holds the k anchors with the largest IoU to ground truth i:
+ * a larger IoU first, among equal IoUs the LOWER anchor index first, NaN as the largest value
+ * (torch.topk's order) -- and a pair with a NaN coordinate in either box has a NaN IoU, as the
+ * same expression has in torch, so a NaN ground truth gets the first k anchors by index and a
+ * NaN anchor is in every bag; the row itself is written in ascending anchor index.  Exact: a radix
+ * select on the IoU's 32 bits, then an ordered compaction.  k < 1, k >
+ * msmd_free_anchor_max_topk() and k > num_anchors (where the reference's topk raises too) are
+ * refused with MSMD_ERR_INVALID_ARG. */
+int msmd_free_anchor_max_topk(void);
+size_t msmd_free_anchor_topk_workspace_bytes(int num_anchors, int num_gt);
+int msmd_free_anchor_topk(const float* anchor_bev /* [num_anchors,4] */, int num_anchors,
+                          const float* gt_bev /* [num_gt,4] */, int num_gt, int k,
+                          int32_t* matched /* [num_gt,k] */, void* workspace,
+                          size_t workspace_bytes, msmd_stream_t stream);
+/* replaces: FreeAnchor3DHead.negative_bag_loss (free_anchor3d_head.py:266-282) and autograd
+ * through it.  sum[0] = sum over all entries of (1 - alpha) p^gamma BCE(p, 0) with
+ * p = clamp(sigmoid(logit) (1 - box_prob), 0, 1) and torch's binary_cross_entropy (the log
+ * clamped at -100, backward p / max((1 - p) p, 1e-12)); grad (optional) = d sum / d logits.
+ * Deterministic: per-block partials in double, summed in block order.  gamma < 1 is refused
+ * (MSMD_ERR_INVALID_ARG): the gradient at p = 0 is unbounded there. */
+size_t msmd_free_anchor_negative_workspace_bytes(int64_t n, int num_classes);
+int msmd_free_anchor_negative_f32(const float* logits /* [n,num_classes] */,
+                                  const float* box_prob /* [n,num_classes] */, int64_t n,
+                                  int num_classes, float gamma, float alpha,
+                                  float* grad /* [n,num_classes] or NULL */, float* sum /* [1] */,
+                                  void* workspace, size_t workspace_bytes, msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

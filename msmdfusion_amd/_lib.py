@@ -217,6 +217,15 @@ SIGNATURES = {
     "msmd_ssd3d_targets_f32": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i,
                                     _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "msmd_nms_mmcv_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    "msmd_decode_nearest_bev_f32": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
+    "msmd_free_anchor_box_prob_workspace_bytes": (_sz, [_i]),
+    "msmd_free_anchor_box_prob_f32": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _f, _vp, _vp, _sz,
+                                           _vp]),
+    "msmd_free_anchor_max_topk": (_i, []),
+    "msmd_free_anchor_topk_workspace_bytes": (_sz, [_i, _i]),
+    "msmd_free_anchor_topk": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "msmd_free_anchor_negative_workspace_bytes": (_sz, [_i64, _i]),
+    "msmd_free_anchor_negative_f32": (_i, [_vp, _vp, _i64, _i, _f, _f, _vp, _vp, _vp, _sz, _vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -425,15 +425,28 @@ def _weighted_mean(loss, weight, avg_factor):
     return (loss.double().sum() / avg_factor).to(loss.dtype)
 
 
+def _elementwise(loss, weight, reduction, override):
+    """mmdet's reduction_override='none' (FreeAnchor3DHead's positive side): the weighted loss,
+    not reduced.  -> None when the class's own reduction applies."""
+    if override is None or override == reduction:
+        return None
+    if override != "none":
+        raise NotImplementedError("reduction_override %r (None or 'none')" % (override,))
+    return loss if weight is None else loss * weight
+
+
 class SmoothL1Loss(nn.Module):
     def __init__(self, beta=1.0, reduction="mean", loss_weight=1.0):
         super().__init__()
         assert reduction == "mean" and beta > 0
         self.beta, self.reduction, self.loss_weight = beta, reduction, loss_weight
 
-    def forward(self, pred, target, weight=None, avg_factor=None):
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None):
         diff = torch.abs(pred - target)
         loss = torch.where(diff < self.beta, 0.5 * diff * diff / self.beta, diff - 0.5 * self.beta)
+        each = _elementwise(loss, weight, self.reduction, reduction_override)
+        if each is not None:
+            return self.loss_weight * each
         return self.loss_weight * _weighted_mean(loss, weight, avg_factor)
 
 
@@ -447,10 +460,13 @@ class CrossEntropyLoss(nn.Module):
             raise NotImplementedError("CrossEntropyLoss: the plain softmax form only")
         self.use_sigmoid, self.reduction, self.loss_weight = use_sigmoid, reduction, loss_weight
 
-    def forward(self, cls_score, label, weight=None, avg_factor=None):
+    def forward(self, cls_score, label, weight=None, avg_factor=None, reduction_override=None):
         loss = F.cross_entropy(cls_score, label, reduction="none")
         if weight is not None:
             weight = weight.float()
+        each = _elementwise(loss, weight, self.reduction, reduction_override)
+        if each is not None:
+            return self.loss_weight * each
         return self.loss_weight * _weighted_mean(loss, weight, avg_factor)
 
 

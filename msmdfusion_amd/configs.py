@@ -482,3 +482,27 @@ def build_head(cfg=None, rows=False):
     args = {k: v for k, v in _PTS_BBOX_HEAD.items() if k != "type"}
     return TransFusionHead(test_cfg=dict(_TEST_CFG_PTS), train_cfg=dict(_TRAIN_CFG_PTS), rows=rows,
                            **args)
+
+
+# ---------------------------------------------------------------------------------------------
+# FreeAnchor (configs/free_anchor/hv_pointpillars_fpn_sbn-all_free-anchor_4x8_2x_nus-3d.py): the
+# `pts_bbox_head` that file puts in place of the base model's (its `_delete_=True` is a merge
+# directive, not a value) and the `train_cfg` it adds.  Ten classes, three FPN levels, eight
+# anchors per cell, code size 9.  The rest of that config -- HardVFE, mmdet's FPN neck, the
+# MVXFasterRCNN detector -- is not built (COVERAGE.md).
+# tests/golden/reference_free_anchor_config.json holds the reference's values.
+FREE_ANCHOR_HEAD_NUS = dict(
+    type="FreeAnchor3DHead", num_classes=10, in_channels=256, feat_channels=256,
+    use_direction_classifier=True, pre_anchor_topk=25, bbox_thr=0.5, gamma=2.0, alpha=0.5,
+    anchor_generator=dict(
+        type="AlignedAnchor3DRangeGenerator", ranges=[[-50, -50, -1.8, 50, 50, -1.8]],
+        scales=[1, 2, 4],
+        sizes=[[0.8660, 2.5981, 1.0], [0.5774, 1.7321, 1.0], [1.0, 1.0, 1.0], [0.4, 0.4, 1]],
+        custom_values=[0, 0], rotations=[0, 1.57], reshape_out=True),
+    assigner_per_size=False, diff_rad_by_sin=True, dir_offset=0.7854, dir_limit_offset=0,
+    bbox_coder=dict(type="DeltaXYZWLHRBBoxCoder", code_size=9),
+    loss_cls=dict(type="FocalLoss", use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=1.0),
+    loss_bbox=dict(type="SmoothL1Loss", beta=1.0 / 9.0, loss_weight=0.8),
+    loss_dir=dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=0.2))
+FREE_ANCHOR_TRAIN_CFG_NUS = dict(
+    pts=dict(code_weight=[1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 0.25, 0.25]))

@@ -25,13 +25,11 @@
 // the non-negative IoU (as pool.hip does): independent of the order of arrival, so the result
 // is bitwise reproducible.  Both passes evaluate the IoU with the same function, which is what
 // the equality test of rule 4 (gt_max_assign_all) relies on.
-#include "common.hpp"
+#include "anchor_common.hpp"
 
 namespace msmd {
 namespace {
 
-constexpr int kAnchorBlock = 256;        // anchors per workgroup: one lane each
-constexpr int kAnchorGtChunk = 128;      // ground-truth boxes staged in LDS at a time
 constexpr int kAnchorMaxSegments = 64;   // segments per call (the table is a kernel argument)
 
 struct AnchorSegments {
@@ -41,18 +39,6 @@ struct AnchorSegments {
   float neg_iou_thr[kAnchorMaxSegments];
   float min_pos_iou[kAnchorMaxSegments];
 };
-
-// mmdet bbox_overlaps(mode='iou', eps=1e-6) on (x1, y1, x2, y2), float32, as written:
-// overlap / max(area1 + area2 - overlap, eps), wh = clamp(rb - lt, 0).
-__device__ __forceinline__ float bev_iou(const float4 g, const float4 a) {
-  const float area_g = (g.z - g.x) * (g.w - g.y);
-  const float area_a = (a.z - a.x) * (a.w - a.y);
-  const float w = fmaxf(fminf(g.z, a.z) - fmaxf(g.x, a.x), 0.f);
-  const float h = fmaxf(fminf(g.w, a.w) - fmaxf(g.y, a.y), 0.f);
-  const float overlap = w * h;
-  const float uni = fmaxf(area_g + area_a - overlap, 1e-6f);
-  return overlap / uni;
-}
 
 // Workgroup b -> (segment, first output row).  Uniform: every lane walks the same table.
 __device__ __forceinline__ bool locate(const AnchorSegments& sg, int& seg, int& row0) {
@@ -68,41 +54,6 @@ __device__ __forceinline__ bool locate(const AnchorSegments& sg, int& seg, int& 
     b -= nb;
   }
   return false;
-}
-
-// The ground-truth list of segment s, clipped to the entries that exist.
-__device__ __forceinline__ int gt_list(const int32_t* __restrict__ gt_offsets, int s, int entries,
-                                       int& begin) {
-  begin = gt_offsets[s];
-  const int end = gt_offsets[s + 1];
-  if (begin < 0 || begin > entries) return 0;
-  const int n = min(end, entries) - begin;
-  return n > 0 ? n : 0;
-}
-
-// Stage entries [c0, c0 + count) of the list into LDS; an index outside [0, num_gt) becomes a
-// NaN box, whose IoU is NaN: it wins no comparison and is never assigned.
-__device__ __forceinline__ void stage_boxes(const float* __restrict__ gt_bev,
-                                            const int32_t* __restrict__ gt_index, int num_gt,
-                                            int first, int count, float4* boxes) {
-  for (int j = threadIdx.x; j < count; j += kAnchorBlock) {
-    const int g = gt_index ? gt_index[first + j] : first + j;
-    float4 v;
-    if ((unsigned)g < (unsigned)num_gt) {
-      const float* p = gt_bev + (size_t)g * 4;
-      v = make_float4(p[0], p[1], p[2], p[3]);
-    } else {
-      const float q = __int_as_float(0x7fc00000);
-      v = make_float4(q, q, q, q);
-    }
-    boxes[j] = v;
-  }
-}
-
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, kWave));
-  return v;
 }
 
 // Pass one: gt_max_bits[entry] = max over the segment's anchors of the IoU's bit pattern.
@@ -276,10 +227,6 @@ __global__ __launch_bounds__(kAnchorBlock) void anchor_targets_kernel(
 constexpr int kSigFocalBlock = 256;
 constexpr int kSigFocalPerThread = 8;
 
-__device__ __forceinline__ float pow_gamma(float v, float gamma) {
-  return gamma == 2.f ? v * v : powf(v, gamma);
-}
-
 // loss_ic = BCE_with_logits(x, t) * (alpha t + (1 - alpha)(1 - t)) * pt^gamma * weight_i,
 // t = [label_i == c], pt = (1 - p) t + p (1 - t), p = sigmoid(x).  Both probabilities are taken
 // from their own exponential, so neither cancels at large |x|.
@@ -312,30 +259,7 @@ __global__ __launch_bounds__(kSigFocalBlock) void sigmoid_focal_kernel(
       grad[i] = t ? dz : -dz;
     }
   }
-  __shared__ double sh[kSigFocalBlock / kWave];
-  for (int off = kWave / 2; off > 0; off >>= 1) loss += __shfl_down(loss, off, kWave);
-  if ((threadIdx.x & (kWave - 1)) == 0) sh[threadIdx.x / kWave] = loss;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double l = 0;
-    for (int k = 0; k < kSigFocalBlock / kWave; ++k) l += sh[k];
-    partial[blockIdx.x] = l;
-  }
-}
-
-// fixed-order sum of the block partials -> out[0]
-__global__ __launch_bounds__(256) void sigmoid_focal_finish_kernel(
-    const double* __restrict__ partial, int blocks, float* __restrict__ out) {
-  __shared__ double sh[256];
-  double l = 0;
-  for (int b = threadIdx.x; b < blocks; b += 256) l += partial[b];
-  sh[threadIdx.x] = l;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = (float)sh[0];
+  block_partial_sum<kSigFocalBlock>(loss, partial);
 }
 
 // The host's half of the segmentation: ascending offsets from 0, at most kAnchorMaxSegments.
@@ -475,7 +399,7 @@ MSMD_EXPORT int msmd_sigmoid_focal_f32(const float* logits, const int64_t* label
   if (blocks > 0)
     MSMD_LAUNCH(sigmoid_focal_kernel, dim3((unsigned)blocks), dim3(kSigFocalBlock), 0, st, logits,
                 labels, weights, (long)n, num_classes, gamma, alpha, grad, (double*)workspace);
-  MSMD_LAUNCH(sigmoid_focal_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)workspace,
+  MSMD_LAUNCH(partials_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)workspace,
               (int)blocks, sum);
   return launch_status();
 }

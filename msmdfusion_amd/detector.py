@@ -54,7 +54,7 @@ def _build_head(cfg, train_cfg, test_cfg, rows):
     args = {k: v for k, v in cfg.items() if k != "type"}
     pts = lambda c: (c or {}).get("pts", c) if isinstance(c, dict) else c
     kind = cfg.get("type", "TransFusionHead")
-    if kind in ("CenterHead", "Anchor3DHead"):
+    if kind in ("CenterHead", "Anchor3DHead", "FreeAnchor3DHead"):
         from .registry import build_head
         return build_head(dict(cfg, train_cfg=pts(train_cfg), test_cfg=pts(test_cfg)))
     if kind != "TransFusionHead":

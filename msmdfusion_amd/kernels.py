@@ -2144,6 +2144,97 @@ def sigmoid_focal(logits, labels, weights, gamma=2.0, alpha=0.25, want_grad=True
     return total, grad
 
 
+# ------------------------------------------------ FreeAnchor3DHead loss (row n6)
+FREE_ANCHOR_MAX_TOPK = lib.msmd_free_anchor_max_topk()
+
+
+def _f32_rows(t, cols, what):
+    t = t.contiguous()
+    if t.dtype != torch.float32 or t.dim() != 2 or (cols is not None and t.shape[1] != cols):
+        raise ValueError("%s must be float32 [n, %s]" % (what, cols if cols else "c"))
+    return t
+
+
+def decode_nearest_bev(anchors, deltas):
+    """DeltaXYZWLHRBBoxCoder.decode followed by nearest_bev for every (sample, anchor):
+    anchors [A, code] float32 shared by the samples, deltas [B * A, code] -> pred_bev [B * A, 4]
+    (x1, y1, x2, y2).  Only the five decoded members the BEV box needs are computed."""
+    _need_cuda(anchors, deltas)
+    a, d = _f32_rows(anchors, None, "anchors"), _f32_rows(deltas, None, "deltas")
+    if a.shape[1] != d.shape[1] or a.shape[0] == 0 or d.shape[0] % a.shape[0]:
+        raise ValueError("deltas holds a whole number of samples of the anchors' rows and code")
+    out = torch.empty((d.shape[0], 4), dtype=torch.float32, device=d.device)
+    check(lib.msmd_decode_nearest_bev_f32(_p(a), a.shape[0], a.shape[1], _p(d),
+                                          d.shape[0] // a.shape[0], _p(out), _stream()),
+          "msmd_decode_nearest_bev_f32")
+    return out
+
+
+def free_anchor_box_prob(pred_bev, gt_bev, gt_labels, gt_offsets, num_classes, bbox_thr):
+    """P{anchor j in A+} of FreeAnchor for a whole batch, without the [G, A] IoU matrix
+    (include/msmd_hip.h, row n6).  pred_bev [B * A, 4]; gt_bev [G, 4], gt_labels long [G];
+    gt_offsets int32 [B + 1] on the device.  -> box_prob float32 [B * A, num_classes]."""
+    _need_cuda(pred_bev, gt_bev, gt_labels, gt_offsets)
+    p, g = _f32_rows(pred_bev, 4, "pred_bev"), _f32_rows(gt_bev, 4, "gt_bev")
+    if gt_offsets.dtype != torch.int32 or gt_offsets.numel() < 2:
+        raise ValueError("gt_offsets must be an int32 tensor of one entry per sample plus one")
+    batch = gt_offsets.numel() - 1
+    if p.shape[0] % batch:
+        raise ValueError("pred_bev holds a whole number of anchors per sample")
+    if gt_labels.dtype != torch.long or gt_labels.numel() != g.shape[0]:
+        raise ValueError("gt_labels must be a long tensor with one entry per box")
+    out = torch.empty((p.shape[0], int(num_classes)), dtype=torch.float32, device=p.device)
+    nbytes = lib.msmd_free_anchor_box_prob_workspace_bytes(g.shape[0])
+    ws = _ws(nbytes, p.device)
+    check(lib.msmd_free_anchor_box_prob_f32(
+        _p(p), batch, p.shape[0] // batch, _p(g), _p(gt_labels.contiguous()), g.shape[0],
+        _p(gt_offsets.contiguous()), int(num_classes), float(bbox_thr), _p(out), _p(ws), nbytes,
+        _stream()), "msmd_free_anchor_box_prob_f32")
+    return out
+
+
+def free_anchor_topk(anchor_bev, gt_bev, k):
+    """The bags of FreeAnchor: for every ground truth the k anchors of largest nearest-BEV IoU
+    (ties to the lower anchor index, NaN largest), each row in ascending anchor index, without
+    the [G, A] matrix.  anchor_bev [A, 4], gt_bev [G, 4] -> matched int32 [G, k]."""
+    _need_cuda(anchor_bev, gt_bev)
+    a, g = _f32_rows(anchor_bev, 4, "anchor_bev"), _f32_rows(gt_bev, 4, "gt_bev")
+    k = int(k)
+    if k > a.shape[0]:
+        raise ValueError("free_anchor_topk: k = %d exceeds the %d anchors (the reference's "
+                         "torch.topk raises there too)" % (k, a.shape[0]))
+    if k < 1 or k > FREE_ANCHOR_MAX_TOPK:
+        raise ValueError("free_anchor_topk: k = %d outside [1, %d]" % (k, FREE_ANCHOR_MAX_TOPK))
+    out = torch.empty((g.shape[0], k), dtype=torch.int32, device=a.device)
+    nbytes = lib.msmd_free_anchor_topk_workspace_bytes(a.shape[0], g.shape[0])
+    ws = _ws(nbytes, a.device)
+    check(lib.msmd_free_anchor_topk(_p(a), a.shape[0], _p(g), g.shape[0], k, _p(out), _p(ws),
+                                    nbytes, _stream()), "msmd_free_anchor_topk")
+    return out
+
+
+def free_anchor_negative(logits, box_prob, gamma=2.0, alpha=0.5, want_grad=True):
+    """FreeAnchor's negative bag loss, summed: (1 - alpha) p^gamma BCE(p, 0) with
+    p = clamp(sigmoid(logits) (1 - box_prob), 0, 1); logits and box_prob float32 [N, C].
+    -> (sum float32 [1], grad like logits | None)"""
+    _need_cuda(logits, box_prob)
+    x, q = _f32_rows(logits, None, "logits"), _f32_rows(box_prob, None, "box_prob")
+    if x.shape != q.shape:
+        raise ValueError("logits and box_prob must have one shape")
+    if not gamma >= 1:
+        raise ValueError("free_anchor_negative: gamma = %r < 1 (the gradient at p = 0 is "
+                         "unbounded)" % (gamma,))
+    n, c = x.shape
+    total = torch.empty((1,), dtype=torch.float32, device=x.device)
+    grad = torch.empty_like(x) if want_grad else None
+    nbytes = lib.msmd_free_anchor_negative_workspace_bytes(n, c)
+    ws = _ws(nbytes, x.device)
+    check(lib.msmd_free_anchor_negative_f32(_p(x), _p(q), n, c, float(gamma), float(alpha),
+                                            _p(grad), _p(total), _p(ws), nbytes, _stream()),
+          "msmd_free_anchor_negative_f32")
+    return total, grad
+
+
 def _sparse_add_fill(feat_a, idx_a, feat_b, idx_b, batch_size, spatial_shape, m, ws_addr,
                      ws_bytes):
     """The union set (m rows) counted into the workspace at ws_addr -> (out_indices, out_feat,

@@ -135,7 +135,8 @@ def build_roi_extractor(cfg):
 
 def build_head(cfg, **kwargs):
     """mmdet3d.models.builder.build_head: CenterHead / SeparateHead (center_head.py),
-    Anchor3DHead (anchor_head.py), VoteHead / BaseConvBboxHead (vote_head.py), SSD3DHead
-    (ssd3d_head.py) and TransFusionHead (head.py)."""
-    from . import anchor_head, center_head, head, ssd3d_head, vote_head  # noqa: F401
+    Anchor3DHead (anchor_head.py), FreeAnchor3DHead (free_anchor_head.py), VoteHead /
+    BaseConvBboxHead (vote_head.py), SSD3DHead (ssd3d_head.py) and TransFusionHead (head.py)."""
+    from . import (anchor_head, center_head, free_anchor_head, head, ssd3d_head,  # noqa: F401
+                   vote_head)
     return HEADS.build(cfg, **kwargs)
