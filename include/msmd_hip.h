@@ -1221,6 +1221,62 @@ int msmd_pillar_pfn_bwd_f32(const float* voxels, const int32_t* num_points,
                             size_t workspace_bytes, msmd_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * p2  HardVFE with one or two VFELayers: decoration + (Linear + BatchNorm1d + ReLU + max over
+ *     the slots) twice, the second layer on [h1; max h1] (csrc/hard_vfe.hip)
+ * replaces: HardVFE.forward   mmdet3d/models/voxel_encoders/voxel_encoder.py (HardVFE)
+ *           VFELayer.forward  mmdet3d/models/voxel_encoders/utils.py:34-106
+ * (the encoder has no gradient to its input).
+ * voxels / num_points / coors as for p1.  flags: 1 with_cluster_center, 2 with_voxel_center.
+ * Decorated row of slot m (K = C + 3 + 3): raw channels, xyz minus (sum over all M slots) /
+ * num_points, x - (coors[3] vx + x_offset), y - (coors[2] vy + y_offset), z - (coors[1] vz +
+ * z_offset); rows with m >= num_points are zero rows and count in both layers' statistics.
+ * Per row: y1 = W1 f, h1 = relu(scale1 y1 + shift1), m1 = max over the slots of h1,
+ * y2 = W2 [h1; m1], out = max over the slots of relu(scale2 y2 + shift2).  u2 == 0: one layer,
+ * out = m1.  Built shapes: K <= 16, u1, u2 <= 64, M <= 64, C >= 3 (else MSMD_ERR_UNSUPPORTED).
+ * N == 0: ok, nothing is launched.  All sums: fp64, added in a fixed order (no atomics). */
+size_t msmd_hard_vfe_workspace_bytes(int num_voxels, int max_points);
+/* The moments of the decorated rows, laid out as msmd_pillar_moments_f32's. */
+int msmd_hard_vfe_moments_f32(const float* voxels, const int32_t* num_points,
+                              const int32_t* coors, int num_voxels, int max_points,
+                              int num_features, int flags, float vx, float vy, float vz,
+                              float x_offset, float y_offset, float z_offset,
+                              double* moments /* [272] */, void* workspace,
+                              size_t workspace_bytes, msmd_stream_t stream);
+/* Layer 2's batch statistics: pivot[u] = y2 of (voxel 0, slot 0), sums[2 u] = sum y2,
+ * sums[2 u + 1] = sum (y2 - pivot)^2 over all N * M rows (u < 64; entries past u2 are 0). */
+int msmd_hard_vfe_stats_f32(const float* voxels, const int32_t* num_points,
+                            const int32_t* coors, int num_voxels, int max_points,
+                            int num_features, int flags, float vx, float vy, float vz,
+                            float x_offset, float y_offset, float z_offset,
+                            const float* w1 /* [u1, K] */, const float* scale1,
+                            const float* shift1, int u1, const float* w2 /* [u2, 2 u1] */,
+                            int u2, float* pivot /* [64] */, double* sums /* [128] */,
+                            void* workspace, size_t workspace_bytes, msmd_stream_t stream);
+/* out[N, U], argmax[N, U] (the smallest slot attaining the maximum of the last layer) and,
+ * with two layers, ymax[N, u2]: y2 at that slot.  U = u2, or u1 when u2 == 0. */
+int msmd_hard_vfe_fwd_f32(const float* voxels, const int32_t* num_points, const int32_t* coors,
+                          int num_voxels, int max_points, int num_features, int flags, float vx,
+                          float vy, float vz, float x_offset, float y_offset, float z_offset,
+                          const float* w1, const float* scale1, const float* shift1, int u1,
+                          const float* w2, const float* scale2, const float* shift2, int u2,
+                          float* out, uint8_t* argmax, float* ymax /* or NULL (u2 == 0) */,
+                          msmd_stream_t stream);
+/* g2[N, U]: the gradient at the last BatchNorm's output, placed at (n, argmax[n, u]).  Two
+ * layers: dy2 = scale2 g2 - (dp + dq y2) per row (dp, dq [u2]: the batch statistics' terms,
+ * zeros in eval mode); sums[u * 128 + j] = dW2[u][j] for the h1 columns j < u1 and
+ * sums[u * 128 + 64 + j] for the m1 columns, then from sums[8192]: [u1 * 17 + k] = sum g1 f_k
+ * (k < 16) and [u1 * 17 + 16] = sum g1, g1 the gradient at the first BatchNorm's output.
+ * One layer: only the [u1][17] block, at sums[0]. */
+int msmd_hard_vfe_bwd_f32(const float* voxels, const int32_t* num_points, const int32_t* coors,
+                          int num_voxels, int max_points, int num_features, int flags, float vx,
+                          float vy, float vz, float x_offset, float y_offset, float z_offset,
+                          const float* w1, const float* scale1, const float* shift1, int u1,
+                          const float* w2, const float* scale2, int u2, const float* g2,
+                          const uint8_t* argmax, const float* dp, const float* dq,
+                          double* sums /* [9280] or [u1 = 64][17] */, void* workspace,
+                          size_t workspace_bytes, msmd_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * n1  PointNet++ op family (csrc/pointnet.hip)
  * replaces: gather_points_ext.gather_points_wrapper / gather_points_grad_wrapper
  *           mmdet3d/ops/gather_points/src/gather_points_cuda.cu:9-94

@@ -188,6 +188,14 @@ SIGNATURES = {
                                      _i, _vp, _vp, _vp]),
     "msmd_pillar_pfn_bwd_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _i,
                                      _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "msmd_hard_vfe_workspace_bytes": (_sz, [_i, _i]),
+    "msmd_hard_vfe_moments_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _sz, _vp]),
+    "msmd_hard_vfe_stats_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _i, _vp, _i,
+                                     _vp, _vp, _vp, _sz, _vp]),
+    "msmd_hard_vfe_fwd_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _i, _vp, _vp,
+                                   _vp, _i, _vp, _vp, _vp, _vp]),
+    "msmd_hard_vfe_bwd_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _i, _vp, _vp,
+                                   _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "msmd_gather_points_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "msmd_group_points_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "msmd_three_nn_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

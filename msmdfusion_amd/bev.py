@@ -134,6 +134,93 @@ class SECONDFPN(nn.Module):
         return [torch.cat(ups, dim=1) if len(ups) > 1 else ups[0]]
 
 
+class ConvModule(nn.Module):
+    """mmcv.cnn.ConvModule in its default order: conv -> norm -> act.  The conv has a bias
+    only without a norm; the norm sits under its abbreviation (`bn`), so the keys are
+    `conv.weight`, `bn.*`."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, padding=0, conv_cfg=None,
+                 norm_cfg=None, act_cfg=dict(type="ReLU"), inplace=True):
+        super().__init__()
+        self.conv = build_conv_layer(conv_cfg, in_channels, out_channels, kernel_size,
+                                     padding=padding, bias=norm_cfg is None)
+        self.norm_name = None
+        if norm_cfg is not None:
+            self.norm_name, norm = build_norm_layer(norm_cfg, out_channels)
+            self.add_module(self.norm_name, norm)
+        if act_cfg is not None and act_cfg.get("type") != "ReLU":
+            raise NotImplementedError("ConvModule: only act_cfg type 'ReLU' (or None) is built")
+        self.activate = None if act_cfg is None else nn.ReLU(inplace=inplace)
+
+    def forward(self, x):
+        x = self.conv(x)
+        if self.norm_name is not None:
+            x = getattr(self, self.norm_name)(x)
+        return x if self.activate is None else self.activate(x)
+
+
+@NECKS.register_module()
+class FPN(nn.Module):
+    """mmdet/models/necks/fpn.py, the subset hv_pointpillars_fpn_nus.py uses: one lateral 1x1
+    ConvModule and one 3x3 ConvModule per used level (`lateral_convs.{i}`, `fpn_convs.{i}`;
+    act_cfg goes to both, not in place), a top-down pass that adds each level, nearest-
+    interpolated to the size of the one below, into it, and the 3x3 convs of the laterals as a
+    tuple.  Extra output levels (num_outs above the used levels, add_extra_convs) are not
+    built.  These are torch / MIOpen convolutions on NCHW maps of any memory format."""
+
+    def __init__(self, in_channels, out_channels, num_outs, start_level=0, end_level=-1,
+                 add_extra_convs=False, conv_cfg=None, norm_cfg=None, act_cfg=None,
+                 upsample_cfg=dict(mode="nearest")):
+        super().__init__()
+        assert isinstance(in_channels, (list, tuple))
+        self.in_channels, self.out_channels = list(in_channels), out_channels
+        self.num_ins, self.num_outs = len(in_channels), num_outs
+        if end_level == -1:
+            self.backbone_end_level = self.num_ins
+        else:
+            self.backbone_end_level = end_level
+            assert end_level <= self.num_ins
+        self.start_level, self.end_level = start_level, end_level
+        used = self.backbone_end_level - start_level
+        if add_extra_convs:
+            raise NotImplementedError("FPN: add_extra_convs is not built")
+        if num_outs > used:
+            raise NotImplementedError("FPN: num_outs=%d above the %d used levels (the extra "
+                                      "max-pool / conv levels) is not built" % (num_outs, used))
+        assert num_outs == used
+        self.upsample_cfg = dict(upsample_cfg)
+        if self.upsample_cfg != dict(mode="nearest"):
+            raise NotImplementedError("FPN: only upsample_cfg=dict(mode='nearest') is built")
+        self.lateral_convs = nn.ModuleList()
+        self.fpn_convs = nn.ModuleList()
+        for i in range(start_level, self.backbone_end_level):
+            self.lateral_convs.append(ConvModule(in_channels[i], out_channels, 1, conv_cfg=conv_cfg,
+                                                 norm_cfg=norm_cfg, act_cfg=act_cfg, inplace=False))
+            self.fpn_convs.append(ConvModule(out_channels, out_channels, 3, padding=1,
+                                             conv_cfg=conv_cfg, norm_cfg=norm_cfg, act_cfg=act_cfg,
+                                             inplace=False))
+        self.init_weights()
+
+    def init_weights(self):
+        """fpn.py: Xavier-uniform on the convs."""
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.xavier_uniform_(m.weight)
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+
+    def forward(self, inputs):
+        if len(inputs) != len(self.in_channels):
+            raise ValueError("FPN got %d maps for %d levels" % (len(inputs), len(self.in_channels)))
+        laterals = [conv(inputs[i + self.start_level])
+                    for i, conv in enumerate(self.lateral_convs)]
+        for i in range(len(laterals) - 1, 0, -1):
+            # (not `+=`: the lateral's ReLU keeps its output for its backward)
+            laterals[i - 1] = laterals[i - 1] + nn.functional.interpolate(
+                laterals[i], size=laterals[i - 1].shape[2:], mode="nearest")
+        return tuple(conv(lat) for conv, lat in zip(self.fpn_convs, laterals))
+
+
 def to_channels_last(module):
     """Weights of every 2-D conv in NHWC (KRSC) order: with a channels-last input
     MIOpen then runs its NHWC kernels and no transpose is inserted per layer."""

@@ -488,8 +488,8 @@ def build_head(cfg=None, rows=False):
 # FreeAnchor (configs/free_anchor/hv_pointpillars_fpn_sbn-all_free-anchor_4x8_2x_nus-3d.py): the
 # `pts_bbox_head` that file puts in place of the base model's (its `_delete_=True` is a merge
 # directive, not a value) and the `train_cfg` it adds.  Ten classes, three FPN levels, eight
-# anchors per cell, code size 9.  The rest of that config -- HardVFE, mmdet's FPN neck, the
-# MVXFasterRCNN detector -- is not built (COVERAGE.md).
+# anchors per cell, code size 9.  The model it is merged into is POINTPILLARS_FPN_NUS below
+# (FREE_ANCHOR_POINTPILLARS_FPN_NUS is the merged result).
 # tests/golden/reference_free_anchor_config.json holds the reference's values.
 FREE_ANCHOR_HEAD_NUS = dict(
     type="FreeAnchor3DHead", num_classes=10, in_channels=256, feat_channels=256,
@@ -506,3 +506,58 @@ FREE_ANCHOR_HEAD_NUS = dict(
     loss_dir=dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=0.2))
 FREE_ANCHOR_TRAIN_CFG_NUS = dict(
     pts=dict(code_weight=[1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 0.25, 0.25]))
+
+
+# ---------------------------------------------------------------------------------------------
+# nuScenes PointPillars with an FPN neck (configs/_base_/models/hv_pointpillars_fpn_nus.py):
+# hard voxelization (64 points per 0.25 m pillar) -> HardVFE (two VFELayers, 64 wide) ->
+# PointPillarsScatter -> SECOND -> FPN -> Anchor3DHead on three levels, as MVXFasterRCNN.
+# tests/golden/reference_pointpillars_fpn_configs.json holds the reference's values.
+_FPN_NUS_VOXEL_SIZE = [0.25, 0.25, 8]
+_FPN_NUS_RANGE = [-50, -50, -5, 50, 50, 3]
+POINTPILLARS_FPN_NUS = dict(
+    type="MVXFasterRCNN",
+    pts_voxel_layer=dict(max_num_points=64, point_cloud_range=_FPN_NUS_RANGE,
+                         voxel_size=_FPN_NUS_VOXEL_SIZE, max_voxels=(30000, 40000)),
+    pts_voxel_encoder=dict(
+        type="HardVFE", in_channels=4, feat_channels=[64, 64], with_distance=False,
+        voxel_size=_FPN_NUS_VOXEL_SIZE, with_cluster_center=True, with_voxel_center=True,
+        point_cloud_range=_FPN_NUS_RANGE,
+        norm_cfg=dict(type="naiveSyncBN1d", eps=1e-3, momentum=0.01)),
+    pts_middle_encoder=dict(type="PointPillarsScatter", in_channels=64, output_shape=[400, 400]),
+    pts_backbone=dict(
+        type="SECOND", in_channels=64,
+        norm_cfg=dict(type="naiveSyncBN2d", eps=1e-3, momentum=0.01), layer_nums=[3, 5, 5],
+        layer_strides=[2, 2, 2], out_channels=[64, 128, 256]),
+    pts_neck=dict(
+        type="FPN", norm_cfg=dict(type="naiveSyncBN2d", eps=1e-3, momentum=0.01),
+        act_cfg=dict(type="ReLU"), in_channels=[64, 128, 256], out_channels=256, start_level=0,
+        num_outs=3),
+    pts_bbox_head=dict(
+        type="Anchor3DHead", num_classes=10, in_channels=256, feat_channels=256,
+        use_direction_classifier=True,
+        anchor_generator=dict(
+            type="AlignedAnchor3DRangeGenerator", ranges=[[-50, -50, -1.8, 50, 50, -1.8]],
+            scales=[1, 2, 4],
+            sizes=[[0.8660, 2.5981, 1.0], [0.5774, 1.7321, 1.0], [1.0, 1.0, 1.0], [0.4, 0.4, 1]],
+            custom_values=[0, 0], rotations=[0, 1.57], reshape_out=True),
+        assigner_per_size=False, diff_rad_by_sin=True, dir_offset=0.7854, dir_limit_offset=0,
+        bbox_coder=dict(type="DeltaXYZWLHRBBoxCoder", code_size=9),
+        loss_cls=dict(type="FocalLoss", use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=1.0),
+        loss_bbox=dict(type="SmoothL1Loss", beta=1.0 / 9.0, loss_weight=1.0),
+        loss_dir=dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=0.2)),
+    train_cfg=dict(pts=dict(
+        assigner=dict(type="MaxIoUAssigner", iou_calculator=dict(type="BboxOverlapsNearest3D"),
+                      pos_iou_thr=0.6, neg_iou_thr=0.3, min_pos_iou=0.3, ignore_iof_thr=-1),
+        allowed_border=0, code_weight=[1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 0.2, 0.2],
+        pos_weight=-1, debug=False)),
+    test_cfg=dict(pts=dict(use_rotate_nms=True, nms_across_levels=False, nms_pre=1000,
+                           nms_thr=0.2, score_thr=0.05, min_bbox_size=0, max_num=500)))
+
+# configs/free_anchor/hv_pointpillars_fpn_sbn-all_free-anchor_4x8_2x_nus-3d.py merged over it as
+# mmcv's Config does: `pts_bbox_head` replaced (`_delete_=True`), `train_cfg.pts` updated key
+# by key.
+FREE_ANCHOR_POINTPILLARS_FPN_NUS = dict(
+    POINTPILLARS_FPN_NUS, pts_bbox_head=FREE_ANCHOR_HEAD_NUS,
+    train_cfg=dict(pts=dict(POINTPILLARS_FPN_NUS["train_cfg"]["pts"],
+                            **FREE_ANCHOR_TRAIN_CFG_NUS["pts"])))

@@ -100,11 +100,12 @@ class TransFusionDetector(nn.Module):
     def _dense(self, cfg, builder, rows_cls):
         """A dense BEV module from its config dict: the torch / MIOpen form, or (rows=True)
         the same parameters and state-dict keys computed on channels-last pixel rows by the
-        sparse-conv kernels (grid_conv.py)."""
+        sparse-conv kernels (grid_conv.py) -- for the type that has a row form (`rows_cls`
+        without its suffix: SECOND, SECONDFPN); any other type is built by the registry."""
         if cfg is None or isinstance(cfg, nn.Module):
             return cfg
-        if not self.rows:
-            return builder(cfg)
+        if not self.rows or cfg.get("type", rows_cls[:-4]) != rows_cls[:-4]:
+            return builder(cfg)      # (a type without a row form, e.g. FPN: the torch form)
         from . import grid_conv
         return getattr(grid_conv, rows_cls)(**{k: v for k, v in cfg.items() if k != "type"})
 
@@ -323,6 +324,51 @@ class VoxelNet(TransFusionDetector):
         metas = img_metas if img_metas is not None else [None] * len(points)
         return [dict(boxes_3d=b, scores_3d=s, labels_3d=l)
                 for b, s, l in self.bbox_head.get_bboxes(*outs, metas, rescale=rescale)]
+
+
+@DETECTORS.register_module()
+class MVXTwoStageDetector(TransFusionDetector):
+    """mmdet3d/models/detectors/mvx_two_stage.py, the point branch: voxelize -> pts_voxel_encoder
+    -> pts_middle_encoder -> pts_backbone -> pts_neck -> pts_bbox_head under the reference's
+    `pts_*` attribute names (its state-dict prefixes), the head called as forward_pts_train
+    (:261-289) and simple_test_pts (:386-396) call it.  The batch size is len(points), not the
+    reference's host read of coors[-1, 0] + 1.  The image branch and pts_fusion_layer are out of
+    scope.  With rows=True the backbone runs on pixel rows and hands the neck NCHW views of its
+    channels-last buffers; an FPN neck (no row form) takes them as they are."""
+
+    def __init__(self, pts_fusion_layer=None, img_rpn_head=None, img_roi_head=None, **kwargs):
+        if pts_fusion_layer is not None or img_rpn_head is not None or img_roi_head is not None:
+            raise NotImplementedError("%s: pts_fusion_layer and the image heads are not built"
+                                      % type(self).__name__)
+        super().__init__(**kwargs)
+
+    def _check_norms(self):
+        for m in self.modules():
+            if hasattr(m, "check_single_process"):     # (the row-form layers bypass forward)
+                m.check_single_process()
+
+    def forward_train(self, *args, **kw):
+        self._check_norms()
+        return super().forward_train(*args, **kw)
+
+    def forward_pts_train(self, pts_feats, img_feats, gt_bboxes_3d, gt_labels_3d, img_metas=None):
+        """mvx_two_stage.py:261-289."""
+        outs = self.pts_bbox_head(pts_feats)
+        return self.pts_bbox_head.loss(*outs, gt_bboxes_3d, gt_labels_3d, img_metas)
+
+    def simple_test(self, points, img_metas=None, img=None, rescale=False, **kw):
+        """mvx_two_stage.py:386-396, 398-412 (bbox3d2result's fields)."""
+        _, pts_feats = self.extract_feat(points, img=img, img_metas=img_metas, **kw)
+        outs = self.pts_bbox_head(pts_feats)
+        metas = img_metas if img_metas is not None else [None] * len(points)
+        return [dict(boxes_3d=b, scores_3d=s, labels_3d=l)
+                for b, s, l in self.pts_bbox_head.get_bboxes(*outs, metas, rescale=rescale)]
+
+
+@DETECTORS.register_module()
+class MVXFasterRCNN(MVXTwoStageDetector):
+    """mmdet3d/models/detectors/mvx_faster_rcnn.py: MVXTwoStageDetector under the name the
+    nuScenes PointPillars-FPN and free_anchor configs use."""
 
 
 @DETECTORS.register_module()

@@ -3009,3 +3009,155 @@ def pillar_pfn_backward(voxels, num_points, coors, geom, weight, scale, shift, m
                                       _p(grad_out), _p(argmax), _p(sums), _p(ws), nbytes,
                                       _stream()), "msmd_pillar_pfn_bwd_f32")
     return sums[:, :k], sums[:, 16]
+
+
+# ------------------------------------------------------------------ HardVFE (csrc/hard_vfe.hip)
+HARD_VFE_MAX_K, HARD_VFE_MAX_U, HARD_VFE_MAX_M = 16, 64, 64
+HARD_VFE_VOXELS_PER_STEP, HARD_VFE_BLOCKS = 4, 512     # kVox, kBlocks of the kernels
+
+
+class HardVFEGeometry:
+    """The decoration a HardVFE applies: flags (1 cluster centre, 2 the three-channel voxel
+    centre), voxel size and centre offsets."""
+
+    def __init__(self, with_cluster_center, with_voxel_center, vx, vy, vz, x_offset, y_offset,
+                 z_offset):
+        self.flags = (1 if with_cluster_center else 0) | (2 if with_voxel_center else 0)
+        self.size = (float(vx), float(vy), float(vz))
+        self.offset = (float(x_offset), float(y_offset), float(z_offset))
+
+    def decorated(self, c):
+        return c + 3 * (self.flags & 1) + 3 * ((self.flags & 2) >> 1)
+
+    def args(self):
+        return (self.flags, *self.size, *self.offset)
+
+
+def hard_vfe_supported(m, c, k, widths):
+    return 1 <= m <= HARD_VFE_MAX_M and c >= 3 and k <= HARD_VFE_MAX_K and \
+        1 <= len(widths) <= 2 and all(1 <= u <= HARD_VFE_MAX_U for u in widths)
+
+
+def _hard_vfe_layers(layers, k):
+    """layers: [(weight, scale, shift)] of one or two layers (scale / shift may be None where
+    the call does not read them) -> (w1, s1, t1, u1, w2, s2, t2, u2)."""
+    if not 1 <= len(layers) <= 2:
+        raise ValueError("the fused HardVFE runs one or two layers, got %d" % len(layers))
+    w1, s1, t1 = layers[0]
+    u1 = int(w1.shape[0])
+    if tuple(w1.shape) != (u1, k) or not w1.is_contiguous():
+        raise ValueError("layer 1 weight must be a contiguous [U1, K=%d] matrix, got %s"
+                         % (k, tuple(w1.shape)))
+    w2 = s2 = t2 = None
+    u2 = 0
+    if len(layers) == 2:
+        w2, s2, t2 = layers[1]
+        u2 = int(w2.shape[0])
+        if tuple(w2.shape) != (u2, 2 * u1) or not w2.is_contiguous():
+            raise ValueError("layer 2 weight must be a contiguous [U2, 2 * U1 = %d] matrix, got %s"
+                             % (2 * u1, tuple(w2.shape)))
+    for t, u, what in ((w1, u1, "weight"), (s1, u1, "scale1"), (t1, u1, "shift1"),
+                       (w2, u2, "weight"), (s2, u2, "scale2"), (t2, u2, "shift2")):
+        if t is None:
+            continue
+        _need_cuda(t)
+        _need_dtype(t, torch.float32, what)
+        if t.dim() == 1 and (t.shape[0] != u or not t.is_contiguous()):
+            raise ValueError("%s must be a contiguous [%d] vector" % (what, u))
+    if u1 > HARD_VFE_MAX_U or u2 > HARD_VFE_MAX_U or k > HARD_VFE_MAX_K:
+        raise ValueError("the fused HardVFE is built for K <= 16 and widths <= 64, got K=%d, "
+                         "widths %s" % (k, (u1, u2)))
+    return w1, s1, t1, u1, w2, s2, t2, u2
+
+
+def _hard_vfe_inputs(voxels, num_points, coors, geom):
+    n, m, c = _pillar_inputs(voxels, num_points, coors)
+    if m > HARD_VFE_MAX_M or c < 3:
+        raise ValueError("the fused HardVFE is built for M <= 64 slots and C >= 3, got M=%d C=%d"
+                         % (m, c))
+    return n, m, c, geom.decorated(c)
+
+
+def hard_vfe_moments(voxels, num_points, coors, geom):
+    """-> (s[K], G[K, K]) float64 of the decorated rows of all N * M slots (pillar_moments with
+    the three-channel centre)."""
+    n, m, c, k = _hard_vfe_inputs(voxels, num_points, coors, geom)
+    dev = voxels.device
+    mom = torch.zeros(272, dtype=torch.float64, device=dev) if n == 0 else \
+        torch.empty(272, dtype=torch.float64, device=dev)
+    nbytes = lib.msmd_hard_vfe_workspace_bytes(n, m)
+    ws = _ws(nbytes, dev)
+    check(lib.msmd_hard_vfe_moments_f32(_p(voxels), _p(num_points), _p(coors), n, m, c,
+                                        *geom.args(), _p(mom), _p(ws), nbytes, _stream()),
+          "msmd_hard_vfe_moments_f32")
+    return mom[:k], mom[16:].view(16, 16)[:k, :k]
+
+
+def hard_vfe_stats(voxels, num_points, coors, geom, w1, scale1, shift1, w2):
+    """Layer 2's pre-BatchNorm sums -> (pivot[U2] float32, sum y2 [U2], sum (y2 - pivot)^2 [U2],
+    float64) over all N * M rows."""
+    n, m, c, k = _hard_vfe_inputs(voxels, num_points, coors, geom)
+    w1, s1, t1, u1, w2, _, _, u2 = _hard_vfe_layers([(w1, scale1, shift1), (w2, None, None)], k)
+    dev = voxels.device
+    pivot = torch.zeros(64, dtype=torch.float32, device=dev)
+    sums = torch.zeros(128, dtype=torch.float64, device=dev)
+    nbytes = lib.msmd_hard_vfe_workspace_bytes(n, m)
+    ws = _ws(nbytes, dev)
+    check(lib.msmd_hard_vfe_stats_f32(_p(voxels), _p(num_points), _p(coors), n, m, c,
+                                      *geom.args(), _p(w1), _p(s1), _p(t1), u1, _p(w2), u2,
+                                      _p(pivot), _p(sums), _p(ws), nbytes, _stream()),
+          "msmd_hard_vfe_stats_f32")
+    sums = sums.view(64, 2)
+    return pivot[:u2], sums[:u2, 0], sums[:u2, 1]
+
+
+def hard_vfe_forward(voxels, num_points, coors, geom, layers):
+    """layers: [(weight, scale, shift)] -> (out[N, U], argmax[N, U] uint8, ymax[N, U] | None):
+    the last layer's maximum, the smallest slot attaining it and (two layers) the
+    pre-BatchNorm y2 there."""
+    n, m, c, k = _hard_vfe_inputs(voxels, num_points, coors, geom)
+    w1, s1, t1, u1, w2, s2, t2, u2 = _hard_vfe_layers(layers, k)
+    u, dev = (u2 or u1), voxels.device
+    out = torch.empty((n, u), dtype=torch.float32, device=dev)
+    arg = torch.empty((n, u), dtype=torch.uint8, device=dev)
+    ymax = torch.empty((n, u), dtype=torch.float32, device=dev) if u2 else None
+    check(lib.msmd_hard_vfe_fwd_f32(_p(voxels), _p(num_points), _p(coors), n, m, c, *geom.args(),
+                                    _p(w1), _p(s1), _p(t1), u1, _p(w2), _p(s2), _p(t2), u2,
+                                    _p(out), _p(arg), _p(ymax), _stream()),
+          "msmd_hard_vfe_fwd_f32")
+    return out, arg, ymax
+
+
+def hard_vfe_backward(voxels, num_points, coors, geom, layers, g2, argmax, dp=None, dq=None):
+    """g2[N, U]: the gradient at the last BatchNorm's output, placed at the argmax slots; dp,
+    dq[U2]: the dense terms of a batch-statistics BatchNorm (dy2 = scale2 g2 - dp - dq y2).
+    -> (dW2[U2, 2 U1] | None, A1[U1, K], sg1[U1]) float64."""
+    n, m, c, k = _hard_vfe_inputs(voxels, num_points, coors, geom)
+    w1, s1, t1, u1, w2, s2, _, u2 = _hard_vfe_layers(layers, k)
+    u, dev = (u2 or u1), voxels.device
+    _need_cuda(g2, argmax, dp, dq)
+    _need_dtype(g2, torch.float32, "g2")
+    _need_dtype(argmax, torch.uint8, "argmax")
+    if tuple(g2.shape) != (n, u) or not g2.is_contiguous() or tuple(argmax.shape) != (n, u) or \
+            not argmax.is_contiguous():
+        raise ValueError("g2 and argmax must be contiguous [N, U] tensors")
+    if u2:
+        for t, what in ((dp, "dp"), (dq, "dq")):
+            _need_dtype(t, torch.float32, what)
+            if tuple(t.shape) != (u2,) or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous [U2] vector" % what)
+    entries = 64 * 128 + 64 * 17 if u2 else 64 * 17
+    sums = torch.zeros(entries, dtype=torch.float64, device=dev)
+    nbytes = lib.msmd_hard_vfe_workspace_bytes(n, m)
+    ws = _ws(nbytes, dev)
+    check(lib.msmd_hard_vfe_bwd_f32(_p(voxels), _p(num_points), _p(coors), n, m, c, *geom.args(),
+                                    _p(w1), _p(s1), _p(t1), u1, _p(w2), _p(s2), u2, _p(g2),
+                                    _p(argmax), _p(dp), _p(dq), _p(sums), _p(ws), nbytes,
+                                    _stream()), "msmd_hard_vfe_bwd_f32")
+    dw2 = None
+    if u2:
+        dw = sums[:8192].view(64, 128)
+        dw2 = torch.cat([dw[:u2, :u1], dw[:u2, 64:64 + u1]], dim=1)
+        sums = sums[8192:]
+    a1 = sums.view(64, 17)
+    return dw2, a1[:u1, :k], a1[:u1, 16]

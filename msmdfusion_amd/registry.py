@@ -10,6 +10,7 @@ dict(type='SubMConv3d', indice_key=...), dict(type='BN1d', eps=1e-3, momentum=0.
 """
 import inspect
 
+from torch import distributed as dist
 from torch import nn
 
 
@@ -68,7 +69,46 @@ NORM_LAYERS.register_module("BN1d", module=nn.BatchNorm1d)
 NORM_LAYERS.register_module("BN2d", module=nn.BatchNorm2d)
 NORM_LAYERS.register_module("BN3d", module=nn.BatchNorm3d)
 
-_NORM_ABBR = {"BN": "bn", "BN1d": "bn", "BN2d": "bn", "BN3d": "bn"}
+
+
+class _NaiveSyncMixin:
+    """mmdet3d/ops/norm.py (NaiveSyncBatchNorm1d / 2d): in a single process -- no process
+    group, or one of world size 1 -- and in eval mode the reference runs plain BatchNorm, and
+    so does this.  Its multi-rank training branch all-reduces the batch mean and mean of
+    squares; that exchange is not built, and normalising with per-rank statistics instead
+    would be a silent deviation, so it is refused."""
+
+    def plain_branch(self):
+        """Whether forward would be plain BatchNorm (what the fused kernels may stand in for)."""
+        return not (self.training and dist.is_available() and dist.is_initialized()
+                    and dist.get_world_size() > 1)
+
+    def check_single_process(self):
+        if not self.plain_branch():
+            raise NotImplementedError(
+                "%s: training with a process group of world size %d needs the all-reduce of the "
+                "batch statistics (mean and mean of squares) across ranks, which is not built; "
+                "per-rank statistics would silently differ from the reference"
+                % (type(self).__name__, dist.get_world_size()))
+
+    def forward(self, input):
+        self.check_single_process()
+        return super().forward(input)
+
+
+class NaiveSyncBatchNorm1d(_NaiveSyncMixin, nn.BatchNorm1d):
+    pass
+
+
+class NaiveSyncBatchNorm2d(_NaiveSyncMixin, nn.BatchNorm2d):
+    pass
+
+
+NORM_LAYERS.register_module("naiveSyncBN1d", module=NaiveSyncBatchNorm1d)
+NORM_LAYERS.register_module("naiveSyncBN2d", module=NaiveSyncBatchNorm2d)
+
+_NORM_ABBR = {"BN": "bn", "BN1d": "bn", "BN2d": "bn", "BN3d": "bn", "naiveSyncBN1d": "bn",
+              "naiveSyncBN2d": "bn"}
 
 
 def build_conv_layer(cfg, *args, **kwargs):
@@ -94,8 +134,8 @@ def build_norm_layer(cfg, num_features, postfix=""):
 def _register_hot_path():
     """Import the modules whose decorators fill the registries (mmdet3d does
     this from its package __init__)."""
-    from . import (bev, multimodal_encoder, pillar_encoder, pointnet2, sparse_encoder,  # noqa: F401
-                   voxel_encoder)
+    from . import (bev, hard_vfe, multimodal_encoder, pillar_encoder, pointnet2,  # noqa: F401
+                   sparse_encoder, voxel_encoder)
     from .spconv import conv  # noqa: F401
 
 
