@@ -1638,6 +1638,82 @@ int msmd_free_anchor_negative_f32(const float* logits /* [n,num_classes] */,
                                   float* grad /* [n,num_classes] or NULL */, float* sum /* [1] */,
                                   void* workspace, size_t workspace_bytes, msmd_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * p3  PointFusion's multi-level image sampler, forward + backward (csrc/point_sample.hip)
+ * replaces: point_sample()  mmdet3d/models/fusion_layers/point_fusion.py:10-95
+ *           PointFusion.obtain_mlvl_feats / sample_single  point_fusion.py:239-306 (the loop
+ *           over samples and levels, one cat per sample and one per batch)
+ *           apply_3d_transformation  mmdet3d/models/fusion_layers/coord_transform.py:7-90
+ *           F.grid_sample(mode='bilinear', padding_mode='zeros') and its backward to the map
+ *           (float atomics in torch)
+ * One call covers all samples and all levels.  points [N, >= 3] are the concatenated clouds
+ * (row stride point_stride floats), sample b owns rows sample_start[b] .. sample_start[b+1]
+ * (the array is given twice: on the DEVICE for the kernels, on the HOST for validation -- 0
+ * first, N last, non-decreasing; an empty sample is fine).  Level l is a channels-last map
+ * [B, H_l, W_l, C_l] and fills columns offset_l .. offset_l + C_l of the [N, sum C_l] output
+ * row; the offsets tile the row in level order.
+ * Per point: q = m [x y z 1]; z = max(q.z, 1e-5); px = q.x / z * scale_x - crop_x (py likewise);
+ * flip != 0: px = img_w - px; per level grid_sample's bilinear unnormalisation of
+ * (px / pad_w * 2 - 1, py / pad_h * 2 - 1) for either align_corners, zero padding (a corner
+ * outside the map contributes nothing; bounds are tested in floating point, coordinates of
+ * 1e30 are fine), corners accumulated nw, ne, sw, se.  float32, no contraction.
+ * Deviation: a point whose pixel coordinate is not finite reads zeros in every level and takes
+ * no part in the backward (torch's result there depends on the backend's float -> int
+ * conversion).  Every output element is written.  N == 0: ok, nothing is launched.
+ * Total cells (B * sum H_l W_l) and N * L * 4 must be below 2^31 (MSMD_ERR_UNSUPPORTED).
+ * ------------------------------------------------------------------------ */
+#define MSMD_POINT_SAMPLE_MAX_LEVELS 8
+typedef struct msmd_point_sample_params { /* one per sample, DEVICE array */
+  float m[12];                            /* 3x4, row-major: detector frame -> homogeneous pixel */
+  float scale_x, scale_y, crop_x, crop_y;
+  float flip;                             /* 0 or 1 */
+  float img_w;                            /* before padding: the flip axis */
+  float pad_h, pad_w;
+} msmd_point_sample_params;
+typedef struct msmd_point_sample_level { /* HOST array, copied into the launch by value */
+  const float* map;                      /* DEVICE [B, h, w, c]; the gradient buffer in bwd */
+  int32_t h, w, c;
+  int32_t offset;                        /* first column of the level in the output row */
+} msmd_point_sample_level;
+int msmd_point_sample_fwd_f32(const float* points, int point_stride, int num_points,
+                              const int32_t* sample_start /* [batch+1] */,
+                              const int32_t* sample_start_host /* host [batch+1] */, int batch,
+                              const msmd_point_sample_params* params /* [batch] */,
+                              const msmd_point_sample_level* levels /* host [num_levels] */,
+                              int num_levels, int align_corners,
+                              float* out /* [num_points, sum c] */, msmd_stream_t stream);
+/* The index of the backward; it depends on the points and the map shapes only.  A contribution
+ * is (point p, level l, corner k), id t = (p L + l) 4 + k: cell[t] = cell_base[l] +
+ * (b H_l + y) W_l + x with cell_base the running sum of B H_l W_l, or -1 for a corner outside
+ * the map or a point that is not finite; weight[t] its bilinear weight (0 where cell is -1).
+ * start [cells + 1] / order [N L 4]: the by-cell inverse, every list in ASCENDING t (built on
+ * msmd_point_inverse_index's stable radix sort).  piece_start [cells + 1]: the exclusive scan of
+ * the number of msmd_point_sample_bwd_chunk()-sized pieces of the lists LONGER than one chunk.
+ * levels[].map is not read (NULL is fine here and in the workspace queries). */
+int msmd_point_sample_bwd_chunk(void);
+size_t msmd_point_sample_index_workspace_bytes(const msmd_point_sample_level* levels,
+                                               int num_levels, int batch, int num_points);
+int msmd_point_sample_index(const float* points, int point_stride, int num_points,
+                            const int32_t* sample_start, const int32_t* sample_start_host,
+                            int batch, const msmd_point_sample_params* params,
+                            const msmd_point_sample_level* levels, int num_levels,
+                            int align_corners, int32_t* cell /* [N L 4] */,
+                            float* weight /* [N L 4] */, int32_t* start /* [cells+1] */,
+                            int32_t* order /* [N L 4] */, int32_t* piece_start /* [cells+1] */,
+                            void* workspace, size_t workspace_bytes, msmd_stream_t stream);
+/* grad_levels[l].map [B, H_l, W_l, C_l] (written, every cell; an empty list gives exact zeros) =
+ * sum over the cell's list, in list order, of weight[t] * grad_out[p, offset_l .. + C_l].
+ * float32; a list longer than one chunk is cut into chunks summed by separate waves into the
+ * workspace, and the partial sums are added in chunk order: no float atomics, the result depends
+ * on the index alone (bitwise reproducible).  There is no gradient to the points. */
+size_t msmd_point_sample_bwd_workspace_bytes(const msmd_point_sample_level* levels,
+                                             int num_levels, int batch, int num_points);
+int msmd_point_sample_bwd_f32(const float* grad_out /* [num_points, sum c] */, int num_points,
+                              int batch, const msmd_point_sample_level* grad_levels,
+                              int num_levels, const float* weight, const int32_t* start,
+                              const int32_t* order, const int32_t* piece_start, void* workspace,
+                              size_t workspace_bytes, msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -234,6 +234,13 @@ SIGNATURES = {
     "msmd_free_anchor_topk": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "msmd_free_anchor_negative_workspace_bytes": (_sz, [_i64, _i]),
     "msmd_free_anchor_negative_f32": (_i, [_vp, _vp, _i64, _i, _f, _f, _vp, _vp, _vp, _sz, _vp]),
+    "msmd_point_sample_fwd_f32": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "msmd_point_sample_bwd_chunk": (_i, []),
+    "msmd_point_sample_index_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "msmd_point_sample_index": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp,
+                                     _vp, _vp, _sz, _vp]),
+    "msmd_point_sample_bwd_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "msmd_point_sample_bwd_f32": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

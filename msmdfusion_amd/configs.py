@@ -561,3 +561,34 @@ FREE_ANCHOR_POINTPILLARS_FPN_NUS = dict(
     POINTPILLARS_FPN_NUS, pts_bbox_head=FREE_ANCHOR_HEAD_NUS,
     train_cfg=dict(pts=dict(POINTPILLARS_FPN_NUS["train_cfg"]["pts"],
                             **FREE_ANCHOR_TRAIN_CFG_NUS["pts"])))
+
+
+# ---------------------------------------------------------------------------------------------
+# MVX-Net on KITTI with dynamic voxelization
+# (configs/mvxnet/dv_mvx-fpn_second_secfpn_adamw_2x8_80e_kitti-3d-3class.py): dynamic
+# voxelization -> DynamicVFE with PointFusion over five image levels -> SparseEncoder -> SECOND
+# -> SECONDFPN -> Anchor3DHead, as DynamicMVXFasterRCNN.  The image backbone and neck (ResNet-50
+# + FPN with five outputs) are injected, as for MSMDFUSION_LC: their entries are left out.
+# tests/golden/reference_mvxnet_config.json holds the reference's values.
+_MVX_VOXEL_SIZE, _MVX_RANGE = [0.05, 0.05, 0.1], [0, -40, -3, 70.4, 40, 1]
+_MVX_TRAIN, _MVX_TEST = _kitti_cfgs(0.35, 0.2)
+MVXNET_DV_SECOND_KITTI = dict(
+    type="DynamicMVXFasterRCNN",
+    pts_voxel_layer=dict(max_num_points=-1, point_cloud_range=_MVX_RANGE,
+                         voxel_size=_MVX_VOXEL_SIZE, max_voxels=(-1, -1)),
+    pts_voxel_encoder=dict(
+        type="DynamicVFE", in_channels=4, feat_channels=[64, 64], with_distance=False,
+        voxel_size=_MVX_VOXEL_SIZE, with_cluster_center=True, with_voxel_center=True,
+        point_cloud_range=_MVX_RANGE,
+        fusion_layer=dict(type="PointFusion", img_channels=256, pts_channels=64,
+                          mid_channels=128, out_channels=128, img_levels=[0, 1, 2, 3, 4],
+                          align_corners=False, activate_out=True, fuse_out=False)),
+    pts_middle_encoder=dict(type="SparseEncoder", in_channels=128, sparse_shape=[41, 1600, 1408],
+                            order=("conv", "norm", "act")),
+    pts_backbone=dict(type="SECOND", in_channels=256, layer_nums=[5, 5], layer_strides=[1, 2],
+                      out_channels=[128, 256]),
+    pts_neck=dict(type="SECONDFPN", in_channels=[128, 256], upsample_strides=[1, 2],
+                  out_channels=[256, 256]),
+    pts_bbox_head=dict(_kitti_anchor_head(512, 40.0), assigner_per_size=True,
+                       assign_per_class=True),
+    train_cfg=dict(pts=_MVX_TRAIN), test_cfg=dict(pts=_MVX_TEST))

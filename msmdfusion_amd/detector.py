@@ -372,6 +372,40 @@ class MVXFasterRCNN(MVXTwoStageDetector):
 
 
 @DETECTORS.register_module()
+class DynamicMVXFasterRCNN(MVXTwoStageDetector):
+    """mmdet3d/models/detectors/mvx_faster_rcnn.py:17-61 (MVX-Net with dynamic voxelization,
+    configs.MVXNET_DV_SECOND_KITTI): the voxel encoder (DynamicVFE) takes the clouds, the image
+    features and the metas and fuses them into the point features through its fusion layer
+    (PointFusion).  The image features come from the injected image branch (extract_img_feat
+    records `input_shape` in the metas) or from an `img_feats=` keyword, whose metas then carry
+    `input_shape` already.  The batch size is len(points)."""
+
+    def extract_feat(self, points, img=None, img_metas=None, img_feats=None, **kw):
+        if img_feats is None:
+            img_feats = self.extract_img_feat(img, img_metas)
+        return img_feats, self.extract_pts_feat(points, img_feats, img_metas, **kw)
+
+    def extract_pts_feat(self, pts, img_feats=None, img_metas=None, prepared=None):
+        """mvx_faster_rcnn.py:46-61 on the prepared scatter index."""
+        if not self.dynamic_voxelization:
+            raise NotImplementedError("DynamicMVXFasterRCNN needs dynamic voxelization "
+                                      "(max_num_points=-1)")
+        feats, coors, planned = prepared if prepared is not None else self.prepare(pts)
+        cat, pts_coors, index = feats
+        feats, coors = self.pts_voxel_encoder(cat, pts_coors, points=pts, img_feats=img_feats,
+                                              img_metas=img_metas, index=index)
+        if hasattr(self.pts_middle_encoder, "plan"):
+            x, _ = self.pts_middle_encoder(feats, coors, len(pts), planned=planned)
+        else:
+            x = self.pts_middle_encoder(feats, coors, len(pts))
+        if self.with_pts_backbone:
+            x = self.pts_backbone(x)
+        if self.with_pts_neck:
+            x = self.pts_neck(x)
+        return x if isinstance(x, (list, tuple)) else [x]
+
+
+@DETECTORS.register_module()
 class VoteNet(nn.Module):
     """mmdet3d/models/detectors/votenet.py on single_stage.py (SingleStage3DDetector): a
     PointNet++ backbone built from BACKBONES and VoteHead, under the reference's attribute

@@ -3161,3 +3161,137 @@ def hard_vfe_backward(voxels, num_points, coors, geom, layers, g2, argmax, dp=No
         sums = sums[8192:]
     a1 = sums.view(64, 17)
     return dw2, a1[:u1, :k], a1[:u1, 16]
+
+
+# ------------------------------------------------------------------ PointFusion's sampler (csrc/point_sample.hip)
+POINT_SAMPLE_MAX_LEVELS = 8
+POINT_SAMPLE_BWD_CHUNK = lib.msmd_point_sample_bwd_chunk()     # kChunk of the kernels
+
+
+class _PointSampleLevel(C.Structure):      # include/msmd_hip.h: msmd_point_sample_level
+    _fields_ = [("map", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32),
+                ("offset", C.c_int32)]
+
+
+class PointSampleBatch:
+    """What one batch of clouds hands the sampler besides the points: sample_start (the host
+    list and its device copy) and the per-sample parameter block [B, 20] float32 on the device
+    (the layout of msmd_point_sample_params)."""
+    __slots__ = ("starts", "sample_start", "params", "batch", "num_points")
+
+    def __init__(self, starts, sample_start, params):
+        self.starts = (C.c_int32 * len(starts))(*starts)
+        self.sample_start, self.params = sample_start, params
+        self.batch, self.num_points = len(starts) - 1, int(starts[-1])
+
+
+def _point_sample_levels(maps):
+    """maps: channels-last contiguous [B, H, W, C] float32 tensors -> (the level array, sum C)."""
+    if not 1 <= len(maps) <= POINT_SAMPLE_MAX_LEVELS:
+        raise ValueError("point_sample: 1..%d levels, got %d" % (POINT_SAMPLE_MAX_LEVELS, len(maps)))
+    levels = (_PointSampleLevel * len(maps))()
+    row = 0
+    for lv, m in zip(levels, maps):
+        _need_cuda(m)
+        _need_dtype(m, torch.float32, "map")
+        if m.dim() != 4 or not m.is_contiguous() or m.shape[0] != maps[0].shape[0]:
+            raise ValueError("point_sample: every map must be a contiguous [B, H, W, C] tensor")
+        lv.map, lv.h, lv.w, lv.c, lv.offset = m.data_ptr(), m.shape[1], m.shape[2], m.shape[3], row
+        row += m.shape[3]
+    return levels, row
+
+
+def _point_sample_shapes(shapes):
+    """The level array of maps known by their (B, H, W, C) only (index, workspace queries)."""
+    levels = (_PointSampleLevel * len(shapes))()
+    row = 0
+    for lv, (_, h, w, c) in zip(levels, shapes):
+        lv.map, lv.h, lv.w, lv.c, lv.offset = None, h, w, c, row
+        row += c
+    return levels
+
+
+def _point_sample_points(points, batch):
+    _need_cuda(points, batch.sample_start, batch.params)
+    _need_dtype(points, torch.float32, "points")
+    if points.dim() != 2 or points.shape[1] < 3 or points.shape[0] != batch.num_points or \
+            (points.shape[0] > 0 and points.stride(1) != 1):
+        raise ValueError("point_sample: points must be [N = %d, >= 3] with unit column stride, got "
+                         "%s" % (batch.num_points, tuple(points.shape)))
+    return points.stride(0) if points.shape[0] > 1 else points.shape[1]
+
+
+def point_sample_forward(points, batch, maps, align_corners):
+    """points [N, >= 3], batch: PointSampleBatch, maps: [B, H_l, W_l, C_l] -> out [N, sum C_l]."""
+    stride = _point_sample_points(points, batch)
+    levels, row = _point_sample_levels(maps)
+    if maps[0].shape[0] != batch.batch:
+        raise ValueError("point_sample: %d samples but maps of batch %d" % (batch.batch,
+                                                                           maps[0].shape[0]))
+    out = torch.empty((batch.num_points, row), dtype=torch.float32, device=points.device)
+    check(lib.msmd_point_sample_fwd_f32(_p(points), stride, batch.num_points,
+                                        _p(batch.sample_start), batch.starts, batch.batch,
+                                        _p(batch.params), levels, len(maps), int(align_corners),
+                                        _p(out), _stream()), "msmd_point_sample_fwd_f32")
+    return out
+
+
+class PointSampleIndex:
+    """The backward's index: per contribution (point, level, corner) its cell and weight, the
+    by-cell lists (start / order) and the scan of the long lists' pieces."""
+    __slots__ = ("cell", "weight", "start", "order", "piece_start", "cells", "num_points")
+
+    def __init__(self, cell, weight, start, order, piece_start, cells, num_points):
+        self.cell, self.weight, self.start, self.order = cell, weight, start, order
+        self.piece_start, self.cells, self.num_points = piece_start, cells, num_points
+
+
+def point_sample_index(points, batch, shapes, align_corners):
+    """The index of point_sample_backward; depends on the points and the maps' (B, H, W, C)
+    shapes only."""
+    stride = _point_sample_points(points, batch)
+    if not 1 <= len(shapes) <= POINT_SAMPLE_MAX_LEVELS:
+        raise ValueError("point_sample: 1..%d levels, got %d" % (POINT_SAMPLE_MAX_LEVELS,
+                                                                 len(shapes)))
+    levels = _point_sample_shapes(shapes)
+    n, nl, dev = batch.num_points, len(shapes), points.device
+    nbytes = lib.msmd_point_sample_index_workspace_bytes(levels, nl, batch.batch, n)
+    if nbytes == 0:
+        raise ValueError("point_sample_index: the cells or the %d x %d x 4 contributions do not "
+                         "fit 31 bits" % (n, nl))
+    cells = sum(int(s[0] * s[1] * s[2]) for s in shapes)
+    t = max(n * nl * 4, 1)
+    cell = torch.empty(t, dtype=torch.int32, device=dev)
+    weight = torch.empty(t, dtype=torch.float32, device=dev)
+    order = torch.empty(t, dtype=torch.int32, device=dev)
+    start = torch.empty(cells + 1, dtype=torch.int32, device=dev)
+    piece_start = torch.empty(cells + 1, dtype=torch.int32, device=dev)
+    ws = _ws(nbytes, dev)
+    check(lib.msmd_point_sample_index(_p(points), stride, n, _p(batch.sample_start), batch.starts,
+                                      batch.batch, _p(batch.params), levels, nl,
+                                      int(align_corners), _p(cell), _p(weight), _p(start),
+                                      _p(order), _p(piece_start), _p(ws), ws.numel(), _stream()),
+          "msmd_point_sample_index")
+    return PointSampleIndex(cell, weight, start, order, piece_start, cells, n)
+
+
+def point_sample_backward(grad_out, index, shapes, grads=None):
+    """grad_out [N, sum C_l] -> the maps' gradients, channels-last [B, H_l, W_l, C_l] (every
+    cell written; `grads`: buffers to write into).  shapes: the maps' (B, H, W, C)."""
+    _need_cuda(grad_out)
+    _need_dtype(grad_out, torch.float32, "grad_out")
+    if grads is None:
+        grads = [torch.empty(tuple(s), dtype=torch.float32, device=grad_out.device)
+                 for s in shapes]
+    levels, row = _point_sample_levels(grads)
+    if tuple(grad_out.shape) != (index.num_points, row) or not grad_out.is_contiguous():
+        raise ValueError("grad_out must be a contiguous [%d, %d] tensor, got %s"
+                         % (index.num_points, row, tuple(grad_out.shape)))
+    b = grads[0].shape[0]
+    nbytes = lib.msmd_point_sample_bwd_workspace_bytes(levels, len(grads), b, index.num_points)
+    ws = _ws(nbytes, grad_out.device)
+    check(lib.msmd_point_sample_bwd_f32(_p(grad_out), index.num_points, b, levels, len(grads),
+                                        _p(index.weight), _p(index.start), _p(index.order),
+                                        _p(index.piece_start), _p(ws), ws.numel(), _stream()),
+          "msmd_point_sample_bwd_f32")
+    return grads

@@ -59,6 +59,7 @@ NECKS = Registry("neck")
 DETECTORS = Registry("detector")
 ROI_EXTRACTORS = Registry("roi_extractor")
 HEADS = Registry("head")
+FUSION_LAYERS = Registry("fusion_layer")
 
 CONV_LAYERS.register_module("Conv1d", module=nn.Conv1d)
 CONV_LAYERS.register_module("Conv2d", module=nn.Conv2d)
@@ -144,8 +145,23 @@ def build_middle_encoder(cfg):
     return MIDDLE_ENCODERS.build(cfg)
 
 
+def build_fusion_layer(cfg):
+    """mmdet3d.models.builder.build_fusion_layer (PointFusion, fusion_layers.py)."""
+    from . import fusion_layers  # noqa: F401
+    return FUSION_LAYERS.build(cfg)
+
+
 def build_voxel_encoder(cfg):
+    """mmdet3d.models.builder.build_voxel_encoder.  A DynamicVFE config carrying a
+    `fusion_layer` dict: the encoder is built without it, the layer by build_fusion_layer, and
+    attached with set_fusion_layer (state-dict prefix `fusion_layer.*`, the reference's).  Any
+    other type goes to its constructor unchanged (HardVFE refuses a fusion layer)."""
     _register_hot_path()
+    if isinstance(cfg, dict) and cfg.get("type") == "DynamicVFE" and \
+            isinstance(cfg.get("fusion_layer"), dict):
+        encoder = VOXEL_ENCODERS.build({k: v for k, v in cfg.items() if k != "fusion_layer"})
+        encoder.set_fusion_layer(build_fusion_layer(cfg["fusion_layer"]))
+        return encoder
     return VOXEL_ENCODERS.build(cfg)
 
 

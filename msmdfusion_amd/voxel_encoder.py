@@ -66,7 +66,12 @@ class DynamicVFE(nn.Module):
 
     with_distance=True reproduces the reference's constructor arithmetic (in_channels + 3
     for the one distance channel appended), whose first Linear then cannot take the
-    decorated features: forward raises instead.  fusion_layer is not built."""
+    decorated features: forward raises instead.
+
+    fusion_layer: the constructor refuses a config dict; registry.build_voxel_encoder builds
+    the layer (PointFusion) and attaches it with set_fusion_layer.  With a layer set and
+    img_feats given, the last vfe layer's point features pass through it before the last
+    scatter (voxel_encoder.py:270-276)."""
 
     def __init__(self, in_channels=4, feat_channels=[], with_distance=False,
                  with_cluster_center=False, with_voxel_center=False, voxel_size=(0.2, 0.2, 4),
@@ -77,7 +82,10 @@ class DynamicVFE(nn.Module):
         assert mode in ["avg", "max"]
         assert len(feat_channels) > 0
         if fusion_layer is not None:
-            raise NotImplementedError("DynamicVFE: fusion_layer is not built")
+            raise NotImplementedError("DynamicVFE: a fusion_layer config is not built by the "
+                                      "constructor; build the encoder with "
+                                      "registry.build_voxel_encoder, which attaches the layer "
+                                      "with set_fusion_layer")
         if with_cluster_center:
             in_channels += 3
         if with_voxel_center:
@@ -110,6 +118,10 @@ class DynamicVFE(nn.Module):
         self.cluster_scatter = DynamicScatter(voxel_size, point_cloud_range, average_points=True)
         self.fusion_layer = None
 
+    def set_fusion_layer(self, module):
+        """Attach the point-image fusion layer (state-dict prefix `fusion_layer.*`)."""
+        self.fusion_layer = module
+
     def map_voxel_center_to_point(self, voxel_feats, index):
         """voxel_feats[M, C] -> [N, C] through the shared index (0 for invalid points)."""
         return gather_points(voxel_feats, index)
@@ -117,7 +129,7 @@ class DynamicVFE(nn.Module):
     def forward(self, features, coors, points=None, img_feats=None, img_metas=None, index=None):
         """features[N, C], coors[N, 4] (batch, z, y, x) -> (voxel_feats[M, C'], voxel_coors[M, 4])
         or, return_point_feats, the last layer's point features."""
-        features = features.float()
+        features = raw = features.float()
         decorated = features.shape[1] + 3 * (self._with_cluster_center + self._with_voxel_center) \
             + int(self._with_distance)
         if decorated != self.vfe_layers[0][0].in_features:
@@ -125,8 +137,11 @@ class DynamicVFE(nn.Module):
                                "layer takes %d (with_distance adds 3 to in_channels but appends "
                                "one channel, as in the reference)"
                                % (decorated, self.vfe_layers[0][0].in_features))
-        if self.fusion_layer is not None or img_feats is not None:
-            raise NotImplementedError("DynamicVFE: fusion_layer is not built")
+        if img_feats is not None and self.fusion_layer is None:
+            raise NotImplementedError("DynamicVFE: img_feats given but no fusion layer is set "
+                                      "(set_fusion_layer / registry.build_voxel_encoder)")
+        if img_feats is not None and (points is None or img_metas is None):
+            raise ValueError("DynamicVFE: fusing img_feats needs points and img_metas")
         if index is None:
             index = scatter_index(coors.contiguous())
         features_ls = [features]
@@ -151,6 +166,11 @@ class DynamicVFE(nn.Module):
         reduce = self.vfe_scatter.reduce_type
         for i, vfe in enumerate(self.vfe_layers):
             point_feats = vfe(features)
+            if i == len(self.vfe_layers) - 1 and self.fusion_layer is not None \
+                    and img_feats is not None:
+                # `features` are the clouds concatenated: the layer need not do it again
+                point_feats = self.fusion_layer(img_feats, points, point_feats, img_metas,
+                                                pts_cat=raw)
             voxel_feats = scatter_reduce(point_feats, index, reduce)
             if i != len(self.vfe_layers) - 1:
                 features = torch.cat([point_feats,
