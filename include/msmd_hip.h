@@ -937,6 +937,35 @@ int msmd_rows_linear_bwd_f32(const float* x, int n, const float* x_tail, int n_t
                              float* dw /* [c_out,c_in] */, float* db /* [c_out] or NULL */,
                              void* workspace, size_t workspace_bytes, msmd_stream_t stream);
 
+/* a16b  both gates computed inside the stage assembly (a15 + a16 in one call each way)
+ * out = msmd_gma_assemble_fwd_f32's, with cross_gate[t] = relu(w_cross feat3[t] + b_cross)
+ * (t = n3: the dummy row) and gate[i] = relu(w_gate feat3[rows_m3[i]] + b_gate) computed
+ * per output row -- the [n3 + 1, c2] table, of which the assembly reads a few per cent, is
+ * never built.  backward: d_conv3 and the weight / bias gradients of both linears, from
+ * per-block partials over the table rows that `order` / `starts` (as a15) refer to; the
+ * ReLU masks are recomputed.  Every value equals the a16 -> a15 chain's to the bit (same
+ * arithmetic, same summation order).  c2 = 64, c3 in {16, 32, 64, 128, 256}
+ * (msmd_gma_stage_supported); weights are nn.Linear's [c2, c3]; biases may be NULL. */
+int msmd_gma_stage_supported(int c3, int c2);
+int msmd_gma_stage_fwd_f32(const float* conv3, int n_o3, int c3, const float* feat3, int n3,
+                           int c2, const float* dummy /* [c3] */, const float* w_cross,
+                           const float* b_cross, const float* w_gate, const float* b_gate,
+                           const int64_t* nn3, const float* feat2, const int64_t* rows_o2,
+                           int n_o2, int n_o2_pad, const int64_t* rows_m3,
+                           const int64_t* rows_m2, int n_mix, int n_mix_pad,
+                           float* out /* [rows, c3 + c2] */, msmd_stream_t stream);
+size_t msmd_gma_stage_bwd_workspace_bytes(int n3, int n_mix, int c3, int c2);
+int msmd_gma_stage_bwd_f32(const float* d_out, int n_o3, int c3, const float* feat3, int n3,
+                           int c2, const float* dummy, const float* w_cross,
+                           const float* b_cross, const float* w_gate, const float* b_gate,
+                           const float* feat2, const int64_t* rows_o2, int n_o2, int n_o2_pad,
+                           const int64_t* rows_m3, const int64_t* rows_m2, int n_mix,
+                           int n_mix_pad, const int64_t* order /* [n_o2] */,
+                           const int64_t* starts /* [n3+2] */, float* d_conv3 /* [n_o3,c3] */,
+                           float* dw_cross /* [c2,c3] */, float* db_cross /* [c2] or NULL */,
+                           float* dw_gate, float* db_gate, void* workspace,
+                           size_t workspace_bytes, msmd_stream_t stream);
+
 /* ------------------------------------------------------------------------ *
  * a14  voxel_modality_split: LiDAR voxels vs virtual-point voxels
  * replaces: MSMDFusionDetector.voxel_modality_split + numba type_assign

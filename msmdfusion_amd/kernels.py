@@ -2389,6 +2389,79 @@ def gma_assemble(conv3, cross_gate, gate, feat3, feat2, nn3, rows_o2, rows_m3, r
                               rows_m2.contiguous(), int(n_o2_pad), int(n_mix_pad), order, starts)
 
 
+def gma_stage_supported(c3, c2):
+    return bool(lib.msmd_gma_stage_supported(int(c3), int(c2)))
+
+
+class _GmaStage(torch.autograd.Function):
+    """Both gate linears inside the stage assembly (csrc/gma.hip): one launch forward, a
+    partial and a reduce launch backward; no gate table is built."""
+
+    @staticmethod
+    def forward(ctx, conv3, w_c, b_c, w_g, b_g, feat3, dummy, feat2, nn3, rows_o2, rows_m3,
+                rows_m2, n_o2_pad, n_mix_pad, order, starts):
+        n_o3, c3 = conv3.shape
+        n3, c2 = feat3.shape[0], feat2.shape[1]
+        n_o2, n_mix = rows_o2.shape[0], rows_m3.shape[0]
+        rows = n_o3 + n_o2 + n_o2_pad + n_mix + n_mix_pad
+        out = torch.empty((rows, c3 + c2), dtype=torch.float32, device=conv3.device)
+        check(lib.msmd_gma_stage_fwd_f32(
+            _p(conv3), n_o3, c3, _p(feat3), n3, c2, _p(dummy), _p(w_c), _p(b_c), _p(w_g), _p(b_g),
+            _p(nn3), _p(feat2), _p(rows_o2), n_o2, n_o2_pad, _p(rows_m3), _p(rows_m2), n_mix,
+            n_mix_pad, _p(out), _stream()), "msmd_gma_stage_fwd_f32")
+        ctx.save_for_backward(w_c, b_c, w_g, b_g, feat3, dummy, feat2, rows_o2, rows_m3, rows_m2,
+                              order, starts)
+        ctx.dims = (n_o3, c3, n3, c2, n_o2, n_o2_pad, n_mix, n_mix_pad)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        w_c, b_c, w_g, b_g, feat3, dummy, feat2, rows_o2, rows_m3, rows_m2, order, starts = \
+            ctx.saved_tensors
+        n_o3, c3, n3, c2, n_o2, n_o2_pad, n_mix, n_mix_pad = ctx.dims
+        d = d_out.contiguous().float()
+        dev = d.device
+        d_conv3 = torch.empty((n_o3, c3), dtype=torch.float32, device=dev)
+        dw_c, dw_g = torch.empty_like(w_c), torch.empty_like(w_g)
+        db_c = None if b_c is None else torch.empty_like(b_c)
+        db_g = None if b_g is None else torch.empty_like(b_g)
+        nbytes = lib.msmd_gma_stage_bwd_workspace_bytes(n3, n_mix, c3, c2)
+        ws = _ws(nbytes, dev)
+        check(lib.msmd_gma_stage_bwd_f32(
+            _p(d), n_o3, c3, _p(feat3), n3, c2, _p(dummy), _p(w_c), _p(b_c), _p(w_g), _p(b_g),
+            _p(feat2), _p(rows_o2), n_o2, n_o2_pad, _p(rows_m3), _p(rows_m2), n_mix, n_mix_pad,
+            _p(order), _p(starts), _p(d_conv3), _p(dw_c), _p(db_c), _p(dw_g), _p(db_g), _p(ws),
+            nbytes, _stream()), "msmd_gma_stage_bwd_f32")
+        return (d_conv3, dw_c, db_c, dw_g, db_g) + (None,) * 11
+
+
+def gma_stage(conv3, w_cross, b_cross, w_gate, b_gate, feat3, dummy, feat2, nn3, rows_o2, rows_m3,
+              rows_m2, n_o2_pad, n_mix_pad, segments):
+    """gma_assemble with both gates computed inside it: cross_gate = relu(Linear(w_cross,
+    b_cross)) of feat3's rows and the `dummy` row [1, c3] behind them, gate = relu(Linear(
+    w_gate, b_gate)) of feat3[rows_m3] -- evaluated per output row, so only the table rows the
+    assembly reads cost anything, forward and backward.  Gradients: conv3 and the four
+    parameters; feat3 / feat2 / dummy get none.  segments = gma_nn_segments(nn3, n3).  The
+    values are those of rows_linear -> gma_assemble to the bit."""
+    _need_cuda(conv3, w_cross, w_gate, feat3, dummy, feat2, nn3, rows_o2, rows_m3, rows_m2)
+    assert not (feat3.requires_grad or feat2.requires_grad or dummy.requires_grad)
+    assert nn3.dtype == rows_o2.dtype == rows_m3.dtype == rows_m2.dtype == torch.int64
+    assert nn3.shape[0] == rows_o2.shape[0] and rows_m3.shape[0] == rows_m2.shape[0]
+    c3, c2 = feat3.shape[1], feat2.shape[1]
+    if not gma_stage_supported(c3, c2):
+        raise ValueError(f"gma_stage: unsupported channels c3 = {c3}, c2 = {c2}")
+    assert conv3.shape[1] == c3 and dummy.numel() == c3
+    assert tuple(w_cross.shape) == tuple(w_gate.shape) == (c2, c3)
+    order, starts = segments
+    assert order.dtype == starts.dtype == torch.int64 and order.shape[0] == nn3.shape[0]
+    assert starts.shape[0] == feat3.shape[0] + 2
+    f = lambda t: None if t is None else t.contiguous().float()
+    return _GmaStage.apply(f(conv3), f(w_cross), f(b_cross), f(w_gate), f(b_gate), f(feat3),
+                           f(dummy), f(feat2), nn3.contiguous(), rows_o2.contiguous(),
+                           rows_m3.contiguous(), rows_m2.contiguous(), int(n_o2_pad),
+                           int(n_mix_pad), order.contiguous(), starts.contiguous())
+
+
 def _modality_split_launch(idx_3d, idx_2d, batch_size, spatial_shape, float_keys,
                            reference_offsets, want_stats):
     """Enqueue one split -> (mix3d, mix2d, pair_3d, pair_2d, out) with out = int32

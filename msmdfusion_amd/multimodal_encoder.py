@@ -88,6 +88,8 @@ class SparseMultiModalEncoderPaint(nn.Module):
         self.fp16_enabled = False
         # one-launch stage assembly (kernels.gma_assemble); MSMD_FUSED_ASSEMBLY=0: the op chain
         self.fused_assembly = os.environ.get("MSMD_FUSED_ASSEMBLY", "1") != "0"
+        # the gate linears inside that launch (kernels.gma_stage); False: rows_linear tables
+        self.fused_gates = True
         # True (set by SparseFusionPath / the detector's `reference_quirks`): batch offsets of
         # the nearest-voxel rows as the reference computes them (:355-369: the PREVIOUS
         # sample's count only) instead of cumulative ones; the same rows for batch <= 2
@@ -438,6 +440,11 @@ class SparseMultiModalEncoderPaint(nn.Module):
             return K.rows_linear(rows, lin.weight, lin.bias, relu=True, x_tail=tail)
         return seq(rows if tail is None else torch.cat([rows, tail], 0))
 
+    @staticmethod
+    def _linear_relu(seq):
+        return (len(seq) == 2 and isinstance(seq[0], nn.Linear) and isinstance(seq[1], nn.ReLU)
+                and seq[0].out_features == 64)
+
     def grouped_sparse_conv(self, voxel_3D, voxel_2D, syn_mix_3D, syn_mix_2D, stage_id, fps_num,
                             radius, max_cluster_samples, dist_thresh, plan=None):
         B = voxel_3D.batch_size
@@ -458,10 +465,35 @@ class SparseMultiModalEncoderPaint(nn.Module):
         # uncovered 2D voxels are gated by a random embedding (row -1 -> last row)
         dummy = plan["dummy"] if "dummy" in plan else \
             self.dummy_embedding_fn(c3, voxel_3D.features.device)
-        cross_gating = self._gate_table(self.cross_gate_control[stage_id], voxel_3D.features,
-                                        dummy.to(voxel_3D.features.dtype))
         n3 = voxel_3D.features.shape[0]
         planned = "unified" in plan     # plan_stage_tensors ran: voxel sets + rulebooks exist
+        stage = f"stage_{stage_id + 1}"
+        # One launch for everything around the convs (csrc/gma.hip) when the stage was planned
+        # ahead and neither input tensor wants a gradient (frozen LiDAR encoder, raw
+        # virtual-point voxels: the LC training configuration); the reference's op-by-op chain
+        # otherwise -- same values.
+        fused = planned and self.fused_assembly and voxel_3D.features.is_cuda and not (
+            voxel_3D.features.requires_grad or voxel_2D.features.requires_grad)
+        # ... with both gates computed inside that launch, for the rows it reads only (the
+        # cross-gate table has n3 + 1 rows, the assembly reads 1-10 % of them) -- same bits
+        if (fused and self.fused_gates and plan.get("nn_segments") is not None
+                and voxel_3D.features.dtype == torch.float32
+                and K.gma_stage_supported(c3, voxel_2D.features.shape[1])
+                and self._linear_relu(self.cross_gate_control[stage_id])
+                and self._linear_relu(self.gate_control[stage_id])):
+            f3_only = voxel_3D.features.index_select(0, only_3D_rows)
+            voxel_only_3D = getattr(self.grouped_sp_conv_blocks_3D, stage)(
+                plan["only3d"].replace_feature(f3_only))
+            lin_c, lin_g = self.cross_gate_control[stage_id][0], self.gate_control[stage_id][0]
+            assert syn_mix_3D.shape[0] == syn_mix_2D.shape[0]
+            feats = K.gma_stage(
+                voxel_only_3D.features, lin_c.weight, lin_c.bias, lin_g.weight, lin_g.bias,
+                voxel_3D.features, dummy.to(voxel_3D.features.dtype), voxel_2D.features,
+                nn3[:only_2D_rows.shape[0]], only_2D_rows, syn_mix_3D, syn_mix_2D,
+                plan["n_pad"], plan["mixed_pad"], plan["nn_segments"])
+            return getattr(self.aggregation_blocks, stage)(plan["unified"].replace_feature(feats))
+        cross_gating = self._gate_table(self.cross_gate_control[stage_id], voxel_3D.features,
+                                        dummy.to(voxel_3D.features.dtype))
         f3_only = voxel_3D.features.index_select(0, only_3D_rows)
         if planned:
             voxel_only_3D = plan["only3d"].replace_feature(f3_only)
@@ -472,12 +504,6 @@ class SparseMultiModalEncoderPaint(nn.Module):
         mixed_3D = voxel_3D.features.index_select(0, syn_mix_3D)
         assert syn_mix_3D.shape[0] == syn_mix_2D.shape[0]
         gate = self._gate_table(self.gate_control[stage_id], mixed_3D)
-        stage = f"stage_{stage_id + 1}"
-        # One launch for the rest (csrc/gma.hip) when the stage was planned ahead and neither
-        # input tensor wants a gradient (frozen LiDAR encoder, raw virtual-point voxels: the
-        # LC training configuration); the reference's op-by-op chain otherwise -- same values.
-        fused = planned and self.fused_assembly and voxel_3D.features.is_cuda and not (
-            voxel_3D.features.requires_grad or voxel_2D.features.requires_grad)
         if fused:
             voxel_only_3D = getattr(self.grouped_sp_conv_blocks_3D, stage)(voxel_only_3D)
             n_o2 = only_2D_rows.shape[0]
