@@ -1743,6 +1743,56 @@ int msmd_point_sample_bwd_f32(const float* grad_out /* [num_points, sum c] */, i
                               const int32_t* order, const int32_t* piece_start, void* workspace,
                               size_t workspace_bytes, msmd_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * p4  ImVoteNet's VoteFusion for the whole batch in one launch (csrc/vote_fusion.hip)
+ * replaces: VoteFusion.forward  mmdet3d/models/fusion_layers/vote_fusion.py:40-212 (the loop
+ *           over samples, the [seed_num, bbox_num, 5 + num_classes] tensors, about sixty
+ *           launches per sample and the topk over the box axis)
+ *           apply_3d_transformation ('DEPTH', both directions), coord_2d_transform,
+ *           bbox_2d_transform  mmdet3d/models/fusion_layers/coord_transform.py:7-214
+ *           Coord3DMode.convert_point (DEPTH <-> CAM with Rt)  core/bbox/structures/
+ *           coord_3d_mode.py:181-257; points_cam2img  core/bbox/structures/utils.py:114-144
+ * seeds [batch, num_seeds, 3] in the detector's depth frame; boxes [total_boxes, 6] = (l, t, r,
+ * b, conf, class) in the rescaled image frame, sample s owning rows box_offsets[s] ..
+ * box_offsets[s+1] (given twice: on the DEVICE for the kernel, on the HOST for validation -- 0
+ * first, total_boxes last, non-decreasing); imgs [batch, 3, pad_h, pad_w] (read only).
+ * Per seed: cam = m_cam [x y z 1]; (u, v) = rint((K cam).xy / (K cam).z - 1), half to even.
+ * Each box is un-rescaled with bbox_2d_transform(ori2new=False)'s float32 operations in its
+ * order (flip, minus crop, divide by scale).  in_box = l < u < r && t < v < b (strict); score =
+ * float(in_box) + conf.  The max_imvote largest scores are kept in descending order, EQUAL SCORES
+ * TO THE LOWER BOX INDEX; a list shorter than max_imvote is filled with score-0 pairs.  Slot k of
+ * seed s is column k * num_seeds + s.  For the chosen boxes: rows 0-1 xz, rows 2-4 ray_angle
+ * (vote_fusion.py:110-150, the offset lifted by m_vote, which includes the forward flow's
+ * translation as the reference does), rows 5 .. 5 + num_classes conf at the class row, all
+ * times float(in_box); mask = floor(score) != 0.  Rows 5 + num_classes .. + 3: the image at
+ * rint(coord_2d_transform(uv, ori2new=True)) divided by 255, the same in every slot of the
+ * seed.  An empty box list gives zero cue rows, mask 1 in slot 0 and 0 in the others.
+ * Deviations: a pixel outside img_h x img_w (or the padded image) or not finite gives a zero
+ * texture cue and is not read; a class outside [0, num_classes) gives no semantic cue; the
+ * image is never written.  Every output element is written, nothing is read back, no atomics.
+ * max_imvote < 1 or > msmd_vote_fusion_max_k(), num_classes < 1 and host offsets that do not
+ * start at 0 / end at total_boxes / decrease are refused (MSMD_ERR_INVALID_ARG).
+ * ------------------------------------------------------------------------ */
+typedef struct msmd_vote_fusion_params { /* one per sample, DEVICE array */
+  float m_cam[12];  /* 3x4, row-major: detector depth frame -> camera frame */
+  float k[9];       /* calib K, row-major */
+  float m_vote[12]; /* 3x4, row-major: camera-frame offset -> detector depth frame */
+  float scale_x, scale_y, crop_x, crop_y;
+  float flip;         /* 0 or 1 */
+  float img_h, img_w; /* img_shape, before padding */
+  float fx;           /* K[0][0], used for both image axes as in the reference */
+} msmd_vote_fusion_params;
+int msmd_vote_fusion_max_k(void); /* largest max_imvote of the fused path */
+int msmd_vote_fusion_f32(const float* seeds /* [batch,num_seeds,3] */, int batch, int num_seeds,
+                         const float* boxes /* [total_boxes,6] */, int total_boxes,
+                         const int32_t* box_offsets /* [batch+1] */,
+                         const int32_t* box_offsets_host /* host [batch+1] */,
+                         const float* imgs /* [batch,3,pad_h,pad_w] */, int pad_h, int pad_w,
+                         const msmd_vote_fusion_params* params /* [batch] */, int num_classes,
+                         int max_imvote,
+                         float* feat /* [batch,5+num_classes+3,max_imvote*num_seeds] */,
+                         uint8_t* mask /* [batch,max_imvote*num_seeds] */, msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -248,6 +248,9 @@ SIGNATURES = {
                                      _vp, _vp, _sz, _vp]),
     "msmd_point_sample_bwd_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "msmd_point_sample_bwd_f32": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "msmd_vote_fusion_max_k": (_i, []),
+    "msmd_vote_fusion_f32": (_i, [_vp, _i, _i, _vp, _i, _vp, _ip, _vp, _i, _i, _vp, _i, _i, _vp, _vp,
+                                  _vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -384,6 +384,43 @@ VOTENET_SCANNET = _votenet(18, 1, False, _SCANNET_MEAN_SIZES)
 
 
 # ---------------------------------------------------------------------------------------------
+# configs/imvotenet/imvotenet_stage2_16x8_sunrgbd-3d-10class.py (type 'ImVoteNet' from its base
+# configs/_base_/models/imvotenet_image.py): VoteNet's backbone, VoteFusion and three VoteHead
+# towers.  The image branch keys of the base (img_backbone, img_neck, img_rpn_head,
+# img_roi_head and their train / test settings) are left out: the 2-D detector is injected.
+# tests/golden/reference_imvotenet_config.json holds the reference's values.
+def _imvotenet_tower(in_channels, conv_channels):
+    vote = _votenet(10, 12, True, _SUNRGBD_MEAN_SIZES)["model"]["bbox_head"]
+    return dict(
+        vote_module_cfg=dict(vote["vote_module_cfg"], in_channels=in_channels,
+                             conv_channels=conv_channels),
+        vote_aggregation_cfg=dict(vote["vote_aggregation_cfg"],
+                                  mlp_channels=[in_channels, 128, 128, 128]))
+
+
+def _imvotenet_stage2():
+    vote = _votenet(10, 12, True, _SUNRGBD_MEAN_SIZES)["model"]
+    common = {k: v for k, v in vote["bbox_head"].items()
+              if k not in ("vote_module_cfg", "vote_aggregation_cfg")}
+    return dict(model=dict(
+        type="ImVoteNet",
+        pts_backbone=vote["backbone"],
+        pts_bbox_heads=dict(common=common, joint=_imvotenet_tower(512, (512, 256)),
+                            pts=_imvotenet_tower(256, (256, 256)),
+                            img=_imvotenet_tower(256, (256, 256)), loss_weights=[0.4, 0.3, 0.3]),
+        img_mlp=dict(in_channel=18, conv_channels=(256, 256), conv_cfg=dict(type="Conv1d"),
+                     norm_cfg=dict(type="BN1d"), act_cfg=dict(type="ReLU")),
+        fusion_layer=dict(type="VoteFusion", num_classes=10, max_imvote_per_pixel=3),
+        num_sampled_seed=1024, freeze_img_branch=True,
+        train_cfg=dict(pts=dict(pos_distance_thr=0.3, neg_distance_thr=0.6, sample_mod="vote")),
+        test_cfg=dict(pts=dict(sample_mod="seed", nms_thr=0.25, score_thr=0.05,
+                               per_class_proposal=True))))
+
+
+IMVOTENET_STAGE2_SUNRGBD = _imvotenet_stage2()
+
+
+# ---------------------------------------------------------------------------------------------
 # 3DSSD (configs/_base_/models/3dssd.py under configs/3dssd/3dssd_kitti-3d-car.py):
 # PointNet2SAMSG + SSD3DHead, one class.  tests/golden/reference_3dssd_config.json holds the
 # reference's values.

@@ -459,6 +459,218 @@ class SSD3DNet(VoteNet):
     SSD3DHead."""
 
 
+class MLP(nn.Module):
+    """mmdet3d/models/utils/mlp.py: (B, C, N) features through kernel-size-1 ConvModules with a
+    conv bias under the norm, keys `mlp.layer{i}.conv.*` / `mlp.layer{i}.bn.*`."""
+
+    def __init__(self, in_channel=18, conv_channels=(256, 256), conv_cfg=dict(type="Conv1d"),
+                 norm_cfg=dict(type="BN1d"), act_cfg=dict(type="ReLU")):
+        super().__init__()
+        from .vote_head import _conv_module
+        self.mlp = nn.Sequential()
+        prev_channels = in_channel
+        for i, conv_channel in enumerate(conv_channels):
+            self.mlp.add_module("layer%d" % i, _conv_module(prev_channels, conv_channel, conv_cfg,
+                                                            norm_cfg, act_cfg, bias=True))
+            prev_channels = conv_channel
+
+    def forward(self, img_features):
+        return self.mlp(img_features)
+
+
+def sample_valid_seeds(mask, num_sampled_seed=1024, generator=None):
+    """imvotenet.py:12-49 for the whole batch, without its nonzero / unique / randperm per
+    sample and their host reads.  mask bool [B, N] -> long [B, num_sampled_seed], per sample by
+    the reference's two branches (chosen with torch.where on the valid count n):
+      n >= num_sampled_seed: a uniformly random num_sampled_seed of the valid indices, in random
+        order (the argsort of uniform keys over the valid entries);
+      n < num_sampled_seed: every valid index in ascending order, then uniformly random distinct
+        members of {0 .. num_sampled_seed - 1} minus {valid % num_sampled_seed}.
+    The draws have the reference's law, not its randperm stream.  generator: a torch.Generator
+    on mask's device."""
+    b, n_all = mask.shape
+    s, dev = int(num_sampled_seed), mask.device
+    mask = mask.bool()
+    count = mask.sum(dim=1, keepdim=True)                                    # [B, 1]
+    take = min(n_all, s)
+    pad = (lambda t: nn.functional.pad(t, (0, s - take))) if take < s else (lambda t: t)
+    # n >= s: the valid entries in random order
+    keys = torch.rand((b, n_all), generator=generator, device=dev)
+    many = pad(torch.argsort(torch.where(mask, keys, keys.new_full((), 2.0)), dim=1)[:, :take])
+    # n < s: the valid entries in ascending order ...
+    pos = torch.arange(n_all, device=dev).expand(b, n_all)
+    ascending = pad(torch.sort(torch.where(mask, pos, pos.new_full((), n_all)), dim=1)[0][:, :take])
+    # ... then the difference set in random order
+    present = torch.zeros((b, s), dtype=torch.int32, device=dev).scatter_add_(
+        1, pos % s, mask.int()) > 0
+    keys2 = torch.rand((b, s), generator=generator, device=dev)
+    rest = torch.argsort(torch.where(present, keys2.new_full((), 2.0), keys2), dim=1)
+    slot = torch.arange(s, device=dev).expand(b, s)
+    few = torch.where(slot < count, ascending, rest.gather(1, (slot - count).clamp(min=0)))
+    return torch.where(count >= s, many, few)
+
+
+@DETECTORS.register_module()
+class ImVoteNet(nn.Module):
+    """mmdet3d/models/detectors/imvotenet.py, stage 2 (forward_train :445-523, simple_test
+    :677-716): a PointNet++ backbone, VoteFusion lifting 2-D detections onto the seeds, and three
+    VoteHead towers (joint / points only / image only) under the reference's attribute names
+    `pts_backbone`, `pts_bbox_head_joint` / `_pts` / `_img`, `img_mlp`, `fusion_layer` (its
+    state-dict prefixes).  The towers are built from pts_bbox_heads.common updated by joint, pts
+    and img; their losses are combined by pts_bbox_heads.loss_weights, non-loss entries come
+    from the joint tower.
+
+    The image branch is INJECTED, as in the MVX detectors: the 2-D detections arrive as
+    `bboxes_2d` (a list of [n, 6] = (l, t, r, b, conf, class) tensors in the rescaled image
+    frame) or from `img_detector(img, img_metas)`, any callable returning that list; it runs
+    under no_grad and its parameters are frozen.  In training half of each list is dropped
+    (a sorted randperm over its length, :352-367).  The image-only pre-training branch
+    (points=None) and aug_test are not built."""
+
+    def __init__(self, pts_backbone=None, pts_bbox_heads=None, pts_neck=None, img_mlp=None,
+                 fusion_layer=None, num_sampled_seed=None, freeze_img_branch=False,
+                 img_detector=None, train_cfg=None, test_cfg=None, pretrained=None, **unused):
+        super().__init__()
+        from .registry import build_fusion_layer, build_head
+        if pts_neck is not None:
+            raise NotImplementedError("ImVoteNet: pts_neck is not built")
+        self.pts_backbone = build_backbone(pts_backbone)
+        pts = lambda c: (c or {}).get("pts", c) if isinstance(c, dict) else c     # noqa: E731
+        heads = dict(pts_bbox_heads)
+        common = dict(heads["common"], train_cfg=pts(train_cfg), test_cfg=pts(test_cfg))
+        self.pts_bbox_head_joint = build_head(dict(common, **heads["joint"]))
+        self.pts_bbox_head_pts = build_head(dict(common, **heads["pts"]))
+        self.pts_bbox_head_img = build_head(dict(common, **heads["img"]))
+        self.loss_weights = list(heads["loss_weights"])
+        self.fusion_layer = build_fusion_layer(fusion_layer)
+        self.max_imvote_per_pixel = self.fusion_layer.max_imvote_per_pixel
+        self.img_mlp = MLP(**img_mlp)
+        self.num_sampled_seed = num_sampled_seed
+        self.freeze_img_branch = freeze_img_branch
+        object.__setattr__(self, "img_detector", img_detector)    # (injected: no keys of ours)
+        if isinstance(img_detector, nn.Module):
+            for p in img_detector.parameters():
+                p.requires_grad = False
+        self.train_cfg, self.test_cfg = train_cfg, test_cfg
+        self.unused_cfg = dict(unused)      # keys of the config this path does not consume
+
+    @property
+    def pts_bbox_heads(self):
+        return [self.pts_bbox_head_joint, self.pts_bbox_head_pts, self.pts_bbox_head_img]
+
+    def extract_pts_feat(self, pts):
+        """:294-304 -> (seed_points, seed_features, seed_indices)."""
+        x = self.pts_backbone(pts)
+        return x["fp_xyz"][-1], x["fp_features"][-1], x["fp_indices"][-1]
+
+    @torch.no_grad()
+    def extract_bboxes_2d(self, img, img_metas, train=True, bboxes_2d=None, generator=None):
+        """:311-368 around the injected detector: the lists as float tensors, in training with
+        half of each dropped."""
+        if bboxes_2d is None:
+            if self.img_detector is None:
+                raise ValueError("ImVoteNet needs bboxes_2d or an injected img_detector")
+            bboxes_2d = self.img_detector(img, img_metas)
+        out = []
+        for ret in bboxes_2d:
+            if len(ret) > 0 and train:
+                keep = torch.randperm(len(ret), generator=generator)[:(len(ret) + 1) // 2]
+                ret = ret[torch.sort(keep)[0].to(ret.device)]
+            out.append(ret.float())
+        return out
+
+    def fuse_and_sample(self, img, bboxes_2d, seeds_3d, seed_3d_features, seed_indices, img_metas,
+                        calib, generator=None):
+        """:452-470: fuse, sample num_sampled_seed imvotes per sample, gather the seed points,
+        features and indices they belong to, img_mlp.  No host read on the fused path.
+        -> (seeds_3d, seed_3d_features, img_features, seed_indices)"""
+        img_features, masks = self.fusion_layer(img, bboxes_2d, seeds_3d, img_metas, calib)
+        inds = sample_valid_seeds(masks, self.num_sampled_seed, generator=generator)
+        batch_size, img_feat_size = img_features.shape[:2]
+        pts_feat_size = seed_3d_features.shape[1]
+        img_features = img_features.gather(
+            -1, inds.view(batch_size, 1, -1).expand(-1, img_feat_size, -1))
+        inds = inds % inds.shape[1]
+        seeds_3d = seeds_3d.gather(1, inds.view(batch_size, -1, 1).expand(-1, -1, 3))
+        seed_3d_features = seed_3d_features.gather(
+            -1, inds.view(batch_size, 1, -1).expand(-1, pts_feat_size, -1))
+        seed_indices = seed_indices.gather(1, inds)
+        return seeds_3d, seed_3d_features, self.img_mlp(img_features), seed_indices
+
+    @staticmethod
+    def _stack(points):
+        return points if torch.is_tensor(points) else torch.stack(list(points))
+
+    def tower_losses(self, points, img, img_metas, calib, bboxes_2d, gt_bboxes_3d, gt_labels_3d,
+                     pts_semantic_mask=None, pts_instance_mask=None, gt_bboxes_ignore=None,
+                     generator=None, drop_generator=None):
+        """The three towers' own loss dicts (joint, pts, img), :445-508.  generator: for the
+        seed sampling, on the points' device; drop_generator: for the half drop, on the CPU."""
+        bboxes_2d = self.extract_bboxes_2d(img, img_metas, bboxes_2d=bboxes_2d,
+                                           generator=drop_generator)
+        points = self._stack(points)
+        seeds_3d, seed_3d_features, seed_indices = self.extract_pts_feat(points)
+        seeds_3d, seed_3d_features, img_features, seed_indices = self.fuse_and_sample(
+            img, bboxes_2d, seeds_3d, seed_3d_features, seed_indices, img_metas, calib,
+            generator=generator)
+        fused_features = torch.cat([seed_3d_features, img_features], dim=1)
+        feats = (fused_features, seed_3d_features, img_features)
+        losses = []
+        for head, f in zip(self.pts_bbox_heads, feats):
+            feat_dict = dict(seed_points=seeds_3d, seed_features=f, seed_indices=seed_indices)
+            preds = head(feat_dict, self.train_cfg["pts"]["sample_mod"])
+            losses.append(head.loss(preds, points, gt_bboxes_3d, gt_labels_3d, pts_semantic_mask,
+                                    pts_instance_mask, img_metas,
+                                    gt_bboxes_ignore=gt_bboxes_ignore))
+        return losses
+
+    def combine_losses(self, losses_towers):
+        """:509-523."""
+        combined = dict()
+        for term in losses_towers[0]:
+            if "loss" in term:
+                combined[term] = 0
+                for i in range(len(losses_towers)):
+                    combined[term] = combined[term] + losses_towers[i][term] * self.loss_weights[i]
+            else:
+                combined[term] = losses_towers[0][term]
+        return combined
+
+    def forward_train(self, points=None, img=None, img_metas=None, calib=None, bboxes_2d=None,
+                      gt_bboxes_3d=None, gt_labels_3d=None, pts_semantic_mask=None,
+                      pts_instance_mask=None, gt_bboxes_ignore=None, generator=None,
+                      drop_generator=None, **kwargs):
+        """:445-523 -> the combined loss dict."""
+        if points is None:
+            raise NotImplementedError("ImVoteNet: the image-only pre-training branch is not built")
+        return self.combine_losses(self.tower_losses(
+            points, img, img_metas, calib, bboxes_2d, gt_bboxes_3d, gt_labels_3d,
+            pts_semantic_mask, pts_instance_mask, gt_bboxes_ignore, generator=generator,
+            drop_generator=drop_generator))
+
+    def simple_test(self, points=None, img_metas=None, img=None, calibs=None, bboxes_2d=None,
+                    rescale=False, generator=None, **kwargs):
+        """:677-716: the joint tower only (bbox3d2result's fields)."""
+        bboxes_2d = self.extract_bboxes_2d(img, img_metas, train=False, bboxes_2d=bboxes_2d)
+        points = self._stack(points)
+        seeds_3d, seed_3d_features, seed_indices = self.extract_pts_feat(points)
+        seeds_3d, seed_3d_features, img_features, seed_indices = self.fuse_and_sample(
+            img, bboxes_2d, seeds_3d, seed_3d_features, seed_indices, img_metas, calibs,
+            generator=generator)
+        feat_dict = dict(seed_points=seeds_3d,
+                         seed_features=torch.cat([seed_3d_features, img_features], dim=1),
+                         seed_indices=seed_indices)
+        bbox_preds = self.pts_bbox_head_joint(feat_dict, self.test_cfg["pts"]["sample_mod"])
+        bbox_list = self.pts_bbox_head_joint.get_bboxes(points, bbox_preds, img_metas,
+                                                        rescale=rescale)
+        return [dict(boxes_3d=b, scores_3d=s, labels_3d=l) for b, s, l in bbox_list]
+
+    def forward(self, points, img_metas=None, return_loss=False, **kw):
+        if return_loss:
+            return self.forward_train(points=points, img_metas=img_metas, **kw)
+        return self.simple_test(points=points, img_metas=img_metas, **kw)
+
+
 _WARNED = {}
 
 

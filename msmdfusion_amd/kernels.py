@@ -3368,3 +3368,48 @@ def point_sample_backward(grad_out, index, shapes, grads=None):
                                         _p(index.piece_start), _p(ws), ws.numel(), _stream()),
           "msmd_point_sample_bwd_f32")
     return grads
+
+
+# ------------------------------------------------------------------ ImVoteNet's VoteFusion (csrc/vote_fusion.hip)
+VOTE_FUSION_MAX_K = lib.msmd_vote_fusion_max_k()
+VOTE_FUSION_PARAMS = 41         # floats of msmd_vote_fusion_params
+
+
+def vote_fusion(seeds, boxes, box_offsets, box_offsets_host, imgs, params, num_classes,
+                max_imvote):
+    """VoteFusion.forward for the whole batch in one launch (msmd_vote_fusion_f32).  seeds
+    float32 [B, S, 3]; boxes float32 [T, 6] (l, t, r, b, conf, class), the samples' lists
+    concatenated; box_offsets int32 [B + 1] on the device and the same numbers as a host
+    sequence; imgs float32 [B, 3, Hpad, Wpad]; params float32 [B, 41] on the device (the layout
+    of msmd_vote_fusion_params) -> (feat float32 [B, 5 + num_classes + 3, K S], mask bool
+    [B, K S]), slot k of seed s in column k S + s."""
+    _need_cuda(seeds, boxes, box_offsets, imgs, params)
+    for t, what in ((seeds, "seeds"), (boxes, "boxes"), (imgs, "imgs"), (params, "params")):
+        _need_dtype(t, torch.float32, what)
+    _need_dtype(box_offsets, torch.int32, "box_offsets")
+    if seeds.dim() != 3 or seeds.shape[2] != 3 or not seeds.is_contiguous():
+        raise ValueError("seeds must be a contiguous float32 [B, S, 3] tensor, got %s"
+                         % (tuple(seeds.shape),))
+    batch, s = seeds.shape[:2]
+    if boxes.dim() != 2 or boxes.shape[1] != 6 or not boxes.is_contiguous():
+        raise ValueError("boxes must be a contiguous float32 [T, 6] tensor, got %s"
+                         % (tuple(boxes.shape),))
+    if imgs.dim() != 4 or imgs.shape[0] != batch or imgs.shape[1] != 3 or not imgs.is_contiguous():
+        raise ValueError("imgs must be a contiguous float32 [B = %d, 3, H, W] tensor, got %s"
+                         % (batch, tuple(imgs.shape)))
+    if tuple(params.shape) != (batch, VOTE_FUSION_PARAMS) or not params.is_contiguous():
+        raise ValueError("params must be a contiguous float32 [%d, %d] tensor, got %s"
+                         % (batch, VOTE_FUSION_PARAMS, tuple(params.shape)))
+    if box_offsets.numel() != batch + 1 or len(box_offsets_host) != batch + 1 or \
+            not box_offsets.is_contiguous():
+        raise ValueError("box_offsets holds B + 1 entries, on the device and on the host")
+    k, classes = int(max_imvote), int(num_classes)
+    host = (C.c_int * (batch + 1))(*[int(v) for v in box_offsets_host])
+    feat = torch.empty((batch, 5 + classes + 3, max(k, 0) * s), dtype=torch.float32,
+                       device=seeds.device)
+    mask = torch.empty((batch, max(k, 0) * s), dtype=torch.uint8, device=seeds.device)
+    check(lib.msmd_vote_fusion_f32(_p(seeds), batch, s, _p(boxes), boxes.shape[0],
+                                   _p(box_offsets), host, _p(imgs), imgs.shape[2], imgs.shape[3],
+                                   _p(params), classes, k, _p(feat), _p(mask), _stream()),
+          "msmd_vote_fusion_f32")
+    return feat, mask.view(torch.bool)
