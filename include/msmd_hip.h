@@ -620,15 +620,17 @@ int msmd_rulebook_plan(const int32_t* nbr, int kernel_volume, int n_rows,
  * one launch set: an index pass plans every table of the step at its end -- nothing in the
  * index chain reads a plan -- with 7 kernels and one radix sort whatever the number of
  * tables (table id = the key's top bits; stable, so each table's order is its own sort's).
- * descs: HOST array.  Per table: order is required, tiled / prefix128 / prefix256 /
- * indice_pairs (+ indice_num) / segtab optional (NULL); prefixes need tiled, segtab needs
- * indice_pairs; ld >= n_rows.  Results identical to the single calls.  Tables the launch
- * set cannot take (kernel volumes whose key needs more than 27 bits, empty tables) run
- * through the single calls inside. */
+ * descs: HOST array.  Per table everything is optional (NULL): order / tiled / prefix128 /
+ * prefix256 / indice_pairs (+ indice_num) / segtab; tiled and the prefixes need order, the
+ * prefixes need tiled, segtab needs indice_pairs; ld >= n_rows.  Tables that ask for no order
+ * are not sorted.  The single-table entry points above run the same kernels on a launch set
+ * of one table, so the results are theirs.  Up to 32 tables share a launch set as long as
+ * table id and sort key fit into 32 bits together (a kernel volume of 16..26 or 28..31 has
+ * a 32-bit key: a set of its own). */
 typedef struct msmd_plan_desc {
   const int32_t* nbr;        /* [K, n_rows] */
   int32_t kvol, n_rows;
-  int32_t* order;            /* [n_rows] */
+  int32_t* order;            /* [n_rows]; required by tiled and the prefixes only */
   int32_t* tiled;            /* [K, n_rows] */
   int32_t* prefix128;        /* [ceil(n_rows / 128) + 1] */
   int32_t* prefix256;        /* [ceil(n_rows / 256) + 1] */

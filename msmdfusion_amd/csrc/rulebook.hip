@@ -4,7 +4,7 @@
 // (nbr[k][o] = input row that reaches output row o through kernel offset k,
 // or -1).  That is the layout the implicit-GEMM kernels (spconv.hip) consume:
 // one coalesced int32 load per (tile row, offset), no atomics, no scatter.
-// msmd_rulebook_pairs() compacts it to the reference's indicePairs/indiceNum
+// msmd_rulebook_pairs() (plan.hip) compacts it to the reference's indicePairs/indiceNum
 // (spconv_ops.h:55-59) for the weight-gradient kernel and for parity checks.
 //
 // SubM (geometry.h:247-297; CUDA indice.cu.h:148-203 uses a dense int32 grid
@@ -494,68 +494,6 @@ __global__ __launch_bounds__(256) void conv_fill(const int32_t* __restrict__ idx
   if (nbr_bwd) nbr_bwd[(size_t)k * n + i] = o;
 }
 
-// ------------------------------------------------- nbr table -> pair list --
-struct NbrValid {
-  const int32_t* nbr;  // one offset's row
-  __device__ int operator()(int i) const { return nbr[i] >= 0; }
-};
-// Compaction of all K offsets in one launch set: element e = k*n_rows + o.
-// Count/Emit see flat element ids; tiles never straddle offsets because each
-// offset is padded to whole tiles (rows_pad).
-struct PairCount {
-  const int32_t* nbr;
-  int n_rows, rows_pad;
-  __device__ int operator()(int e) const {
-    int k = e / rows_pad, o = e - k * rows_pad;
-    return o < n_rows && nbr[(size_t)k * n_rows + o] >= 0;
-  }
-};
-// Compaction of one offset's neighbours into the reference's pair lists, with the tail of
-// both rows filled with -1 (the reference allocates indicePairs as full(-1),
-// spconv_ops.h:55-59) by the table's EMPTY entries: entry o of offset k without a
-// neighbour, the r-th such, writes position num_k + r.  No 0xFF fill of the whole
-// [K,2,ld] tensor in front (19 MB per table at 90k rows, 12 tables per LC step), no scan of
-// the tile sums, no separate count kernel: a block adds up the tile sums it needs.
-__global__ __launch_bounds__(kScanBlock) void pairs_apply_kernel(
-    const int32_t* __restrict__ nbr, int n_rows, int rows_pad, int ld, int kvol,
-    const int* __restrict__ tile_sums, int32_t* __restrict__ pairs, int32_t* __restrict__ num) {
-  __shared__ int smem[kScanSmem];
-  const int tpk = rows_pad / kScanTile;
-  const int k = blockIdx.x / tpk, tile_in_k = blockIdx.x - k * tpk;
-  // pairs of this offset in front of this tile, and in the whole offset
-  int carry = block_range_sum<kScanBlock>(tile_sums, k * tpk, (int)blockIdx.x, smem);
-  const int num_k = carry + block_range_sum<kScanBlock>(tile_sums, (int)blockIdx.x, (k + 1) * tpk, smem);
-  if (tile_in_k == 0 && threadIdx.x == 0) num[k] = num_k;
-  int32_t* pin = pairs + ((size_t)k * 2 + 0) * ld;
-  int32_t* pout = pin + ld;
-  const int base = tile_in_k * kScanTile;
-  int src[kScanItems], v[kScanItems], ex[kScanItems];
-#pragma unroll
-  for (int j = 0; j < kScanItems; ++j) {
-    const int o = base + j * kScanBlock + threadIdx.x;
-    src[j] = o < n_rows ? nbr[(size_t)k * n_rows + o] : -1;
-    v[j] = src[j] >= 0;
-  }
-  tile_excl_scan(v, ex, smem);
-#pragma unroll
-  for (int j = 0; j < kScanItems; ++j) {
-    const int o = base + j * kScanBlock + threadIdx.x;
-    const int pos = carry + ex[j];         // pairs of offset k in front of entry o
-    if (v[j]) {
-      if (pos < ld) {
-        pin[pos] = src[j];
-        pout[pos] = o;
-      }
-    } else {
-      const int tail = num_k + (o - pos);  // o - pos = empty entries in front of o
-      if (tail < ld) {
-        pin[tail] = -1;
-        pout[tail] = -1;
-      }
-    }
-  }
-}
-
 int check_geom(const int* shape, const int* ks, const int* st, const int* pd, int batch,
                Geom* g) {
   const int grid = check_grid(batch, shape, g->shape);
@@ -681,7 +619,7 @@ MSMD_EXPORT int msmd_rulebook_subm3d_bitmap(const int32_t* indices, int n, int b
 
 // ------------------------------------------------- SubM, many tables --------
 // The SubM tables of an index pass in one launch set (msmd_rulebook_subm3d_many).  Like the
-// plans (plan_many.hip) nothing in the index chain reads a SubM table -- the feature pass and
+// plans (plan.hip) nothing in the index chain reads a SubM table -- the feature pass and
 // the planning do -- so the ~12 tables of an LC step are built together at the end of
 // prepare(): 2 fills + 6 kernels instead of 3 (hash index) or 10 (bitmap index) launches
 // each.  Per table the same index structure and the same kernels' arithmetic as the single
@@ -1200,49 +1138,5 @@ MSMD_EXPORT int msmd_rulebook_add_conv_count_chain(const int32_t* const* extra, 
     prev = w;
     base += cb;
   }
-  return launch_status();
-}
-
-// ------------------------------------------------------------ pair lists ---
-namespace {
-inline int rows_padded(int n_rows) { return scan_num_tiles(n_rows > 0 ? n_rows : 1) * kScanTile; }
-}
-
-MSMD_EXPORT size_t msmd_rulebook_pairs_workspace_bytes(int kernel_volume, int n_rows) {
-  ArenaSize a;
-  a.take<int>((size_t)kernel_volume * (rows_padded(n_rows) / kScanTile) + 1);
-  a.take<int>(64);
-  return a.off;
-}
-
-MSMD_EXPORT int msmd_rulebook_pairs(const int32_t* nbr, int kernel_volume, int n_rows,
-                                    int32_t* indice_pairs, int ld, int32_t* indice_num,
-                                    void* workspace, size_t workspace_bytes,
-                                    msmd_stream_t stream) {
-  if (kernel_volume < 1 || n_rows < 0 || ld < 0 || !indice_num ||
-      (n_rows > 0 && (!nbr || !indice_pairs)))
-    return MSMD_ERR_INVALID_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int rp = rows_padded(n_rows), tpk = rp / kScanTile;
-  if ((double)kernel_volume * rp >= 2147483647.0) return MSMD_ERR_RANGE;
-  Arena a(workspace, workspace_bytes);
-  int* tiles = a.take<int>((size_t)kernel_volume * tpk + 1);
-  int* total = a.take<int>(64);
-  if (!a.ok()) return MSMD_ERR_WORKSPACE;
-  // (entries past rows_pad -- ld larger than the padded table -- are not reached by the
-  // empty entries' -1 writes)
-  if (ld > rp)
-    hipMemsetAsync(indice_pairs, 0xFF, sizeof(int32_t) * (size_t)kernel_volume * 2 * ld, st);
-  if (n_rows == 0) {
-    if (ld > 0 && ld <= rp)
-      hipMemsetAsync(indice_pairs, 0xFF, sizeof(int32_t) * (size_t)kernel_volume * 2 * ld, st);
-    hipMemsetAsync(indice_num, 0, sizeof(int32_t) * kernel_volume, st);
-    return launch_status();
-  }
-  (void)total;
-  MSMD_LAUNCH(scan_tile_sums<PairCount>, dim3(kernel_volume * tpk), dim3(kScanBlock), 0, st,
-              PairCount{nbr, n_rows, rp}, kernel_volume * rp, tiles);
-  MSMD_LAUNCH(pairs_apply_kernel, dim3(kernel_volume * tpk), dim3(kScanBlock), 0, st, nbr, n_rows,
-              rp, ld, kernel_volume, (const int*)tiles, indice_pairs, indice_num);
   return launch_status();
 }

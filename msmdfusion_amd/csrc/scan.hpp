@@ -19,6 +19,9 @@ constexpr int kScanItems = 8;
 constexpr int kScanTile = kScanBlock * kScanItems;
 
 inline int scan_num_tiles(long n) { return ceil_div(n, kScanTile); }
+// Rows of a table padded to whole scan tiles (the pair compaction: each offset's rows are a
+// run of whole tiles, so no tile straddles two offsets).
+inline int rows_padded(int n_rows) { return scan_num_tiles(n_rows > 0 ? n_rows : 1) * kScanTile; }
 
 template <typename Count>
 __global__ __launch_bounds__(kScanBlock) void scan_tile_sums(Count count, int n,
@@ -94,6 +97,30 @@ __device__ __forceinline__ int tile_excl_scan(const int (&v)[kScanItems], int (&
   }
   __syncthreads();      // smem may be written again
   return run;
+}
+
+// In place, by ONE block of 1024 threads: a[0..n) values -> a[0..n] exclusive prefix (a has
+// n + 1 entries; the stream-K tile weights of a table).  part: 1024 ints of LDS.
+__device__ __forceinline__ void block_prefix_in_place(int32_t* __restrict__ a, int n, int* part) {
+  const int per = (n + 1023) / 1024, t = threadIdx.x;
+  const int b = t * per, e = b + per < n ? b + per : n;
+  int s = 0;
+  for (int i = b; i < e; ++i) s += a[i];
+  part[t] = s;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {
+    const int v = t >= o ? part[t - o] : 0;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  int run = part[t] - s;    // exclusive prefix of this thread's slice
+  for (int i = b; i < e; ++i) {
+    const int w = a[i];
+    a[i] = run;
+    run += w;
+  }
+  if (t == 1023) a[n] = part[1023];
 }
 
 // total <- 0 for an empty input

@@ -482,17 +482,7 @@ __global__ __launch_bounds__(256) void row_mask_kernel(const int32_t* __restrict
                           : (long long)(v >> 1);
 }
 
-// The same key in 32 bits (K <= 31), for the in-library radix sort (tiling.hip).
-__global__ __launch_bounds__(256) void row_key32_kernel(const int32_t* __restrict__ nbr, int kvol,
-                                                        int n, uint32_t* __restrict__ key,
-                                                        int32_t* __restrict__ row_ids) {
-  int o = blockIdx.x * 256 + threadIdx.x;
-  if (o >= n) return;
-  if (row_ids) row_ids[o] = o;          // the sort's payload (was a launch of its own)
-  // (the Gray code of the ranked mask simulates 1.3 % better, 1.299 -> 1.282 items / useful
-  // work; measured within noise, not used)
-  key[o] = row_key32(nbr, kvol, (size_t)n, o);
-}
+// (The same key in 32 bits, K <= 31, for the in-library radix sort: tiling_key.hpp, plan.hip.)
 
 // cost[t] = K - |union of the masks of tile t's rows| (ascending = heaviest first),
 // tile t = positions [t * rows, (t+1) * rows) of `order`.  One block per tile.
@@ -812,21 +802,6 @@ MSMD_EXPORT int msmd_rulebook_row_masks(const int32_t* nbr, int kernel_volume, i
               nbr, kernel_volume, n_rows, (unsigned long long*)masks, (long long*)sort_keys);
   return launch_status();
 }
-
-namespace msmd {
-// for tiling.hip: 32-bit sort keys (and how many of their bits matter) / tile costs
-void launch_row_keys(const int32_t* nbr, int kvol, int n, uint32_t* keys, int32_t* row_ids,
-                     int* key_bits, hipStream_t st) {
-  MSMD_LAUNCH(row_key32_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, nbr, kvol, n, keys,
-              row_ids);
-  *key_bits = row_key_bits(kvol);
-}
-void launch_tile_costs(const int32_t* nbr, int kvol, int n, const int32_t* order, int rows,
-                       int32_t* cost, int32_t* tile_ids, hipStream_t st) {
-  MSMD_LAUNCH(tile_cost_kernel, dim3(ceil_div(n, rows)), dim3(128), 0, st, nbr, kvol, n, order,
-              rows, cost, tile_ids);
-}
-}  // namespace msmd
 
 MSMD_EXPORT int msmd_rulebook_tile_costs(const int32_t* nbr, int kernel_volume, int n_rows,
                                          const int32_t* order, int rows_per_tile, int32_t* cost,

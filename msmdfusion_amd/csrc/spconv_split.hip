@@ -25,6 +25,7 @@
 //
 // Forward / dgrad: output-stationary pipelined implicit GEMM (see the kernel).
 #include "common.hpp"
+#include "scan.hpp"
 
 #include <type_traits>
 
@@ -1245,27 +1246,8 @@ __global__ __launch_bounds__(256) void tile_weight_kernel(const int32_t* __restr
   if (threadIdx.x == 0) weight[blockIdx.x] = s_total > 0 ? s_total : 1;
 }
 __global__ __launch_bounds__(1024) void tile_prefix_kernel(int32_t* __restrict__ a, int n) {
-  // in place: a[0..n) weights -> a[0..n] exclusive prefix (a has n + 1 entries)
   __shared__ int part[1024];
-  const int per = (n + 1023) / 1024, t = threadIdx.x;
-  const int b = t * per, e = b + per < n ? b + per : n;
-  int s = 0;
-  for (int i = b; i < e; ++i) s += a[i];
-  part[t] = s;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {
-    const int v = t >= o ? part[t - o] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  int run = part[t] - s;    // exclusive prefix of this thread's slice
-  for (int i = b; i < e; ++i) {
-    const int w = a[i];
-    a[i] = run;
-    run += w;
-  }
-  if (t == 1023) a[n] = part[1023];
+  block_prefix_in_place(a, n, part);
 }
 
 // ------------------------------------------------------------------ wgrad --
@@ -1672,7 +1654,7 @@ MSMD_EXPORT int msmd_rulebook_permute_cols(const int32_t* nbr, int kvol, int ld,
 // caller finishes with that entry point's reduction (see msmd_spconv_wgrad_split
 // in spconv.hip).
 namespace msmd {
-int stream_k_c1() { return sk_c1(); }     // plan_many.hip: the tile weights of all tables
+int stream_k_c1() { return sk_c1(); }     // plan.hip: the tile weights from the sorted keys
 int wgrad_split_partials(const float* in_feat, int c_in, const float* d_out, int c_out,
                          const int32_t* pairs, const int32_t* num, int ld, int kvol, int np,
                          int nchunks, float* ws, hipStream_t st) {

@@ -1,5 +1,5 @@
-// tiling_key.hpp -- the 32-bit sort key a table row gets in the tiling order (spconv.hip:
-// row_key32_kernel, plan_many.hip: keys_many_kernel; the reasoning sits at row_mask_kernel).
+// tiling_key.hpp -- the 32-bit sort key a table row gets in the tiling order (plan.hip:
+// keys_many_kernel; the reasoning sits at spconv.hip: row_mask_kernel).
 #pragma once
 #include "common.hpp"
 

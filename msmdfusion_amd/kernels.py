@@ -1081,7 +1081,7 @@ class _PlanDesc(C.Structure):      # include/msmd_hip.h: msmd_plan_desc (80 byte
 
 def rulebook_plan_many(jobs):
     """rulebook_plan (+ the one-chunk pair_segments table) of MANY tables in one library call
-    and one launch set (csrc/plan_many.hip).  jobs: dicts with nbr [K,n] and optionally
+    and one launch set (csrc/plan.hip).  jobs: dicts with nbr [K,n] and optionally
     tile_rows (heights, 128 / 256; implies the tile-ordered table), want_table, want_pairs,
     want_segments (implies pairs), ld.  -> one dict per job:
     order, tiled | None, prefix {rows: tensor}, pairs (pairs, num) | None,

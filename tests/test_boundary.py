@@ -101,6 +101,63 @@ def test_host_side_argument_validation():
     assert lib.msmd_device_ok() in (0, 1)
 
 
+def test_planning_calls_refuse_bad_arguments_host_side():
+    """msmd_rulebook_tiling / _plan / _pairs / _plan_many validate everything before the first
+    launch.  The codes are the ones the table-by-table implementation returned (recorded
+    there; msmd_rulebook_plan's two pair-list checks ran after its tiling launches there and
+    returned the same code): the single-table calls are launch sets of one table now."""
+    from msmdfusion_amd import kernels as K
+    from msmdfusion_amd._lib import lib
+    p, big = ctypes.c_void_p(256), 1 << 24        # (never dereferenced: every call is refused)
+    INVALID, WORKSPACE, UNSUPPORTED, RANGE = -1, -2, -3, -5
+    plan = lib.msmd_rulebook_plan
+    assert plan(p, 27, 0, 128, p, p, None, None, None, 0, None, p, big, None) == INVALID   # no rows
+    assert plan(p, 27, 10, 128, None, p, None, None, None, 0, None, p, big, None) == INVALID
+    assert plan(p, 27, 10, 128, p, None, None, None, None, 0, None, p, big, None) == INVALID
+    assert plan(p, 40, 10, 128, p, p, None, None, None, 0, None, p, big, None) == UNSUPPORTED
+    assert plan(p, 27, 10, 128, p, p, None, None, p, 10, None, p, big, None) == INVALID   # no num
+    assert plan(p, 27, 10, 128, p, p, None, None, p, 9, p, p, big, None) == INVALID       # ld < n
+    assert plan(p, 27, 10, 128, p, p, None, None, None, 0, None, p, 0, None) == WORKSPACE
+    assert plan(p, 27, 10, 128, p, p, None, None, None, 0, None, ctypes.c_void_p(260), big,
+                None) == WORKSPACE
+    tiling = lib.msmd_rulebook_tiling
+    assert tiling(p, 0, 10, 128, p, p, p, big, None) == UNSUPPORTED
+    assert tiling(p, 32, 10, 128, p, p, p, big, None) == UNSUPPORTED
+    assert tiling(p, 27, -1, 128, p, p, p, big, None) == INVALID
+    assert tiling(p, 27, 10, 0, p, p, p, big, None) == INVALID
+    assert tiling(p, 27, 10, 128, None, p, p, big, None) == INVALID
+    assert tiling(None, 27, 0, 128, None, None, None, 0, None) == 0                       # empty: ok
+    assert tiling(p, 27, 10, 128, p, None, p, 0, None) == WORKSPACE
+    pairs = lib.msmd_rulebook_pairs
+    assert pairs(p, 0, 10, p, 10, p, p, big, None) == INVALID
+    assert pairs(p, 125, 10, p, 10, None, p, big, None) == INVALID
+    assert pairs(p, 125, 10, p, -1, p, p, big, None) == INVALID
+    assert pairs(p, 125, 10, None, 10, p, p, big, None) == INVALID
+    assert pairs(p, 4096, 1 << 20, p, 1 << 20, p, p, big, None) == RANGE
+    assert pairs(p, 125, 10, p, 10, p, p, 0, None) == WORKSPACE
+    many = lib.msmd_rulebook_plan_many
+
+    def desc(**kw):
+        d = (K._PlanDesc * 1)()
+        for k, v in dict(dict(nbr=256, kvol=27, n_rows=10, order=256, ld=10), **kw).items():
+            setattr(d[0], k, v)
+        return d
+    assert many(desc(), -1, p, big, None) == INVALID
+    assert many(None, 1, p, big, None) == INVALID
+    assert many(None, 0, None, 0, None) == 0
+    assert many(desc(), 1, None, big, None) == WORKSPACE
+    assert many(desc(), 1, p, 0, None) == WORKSPACE
+    assert many(desc(kvol=40), 1, p, big, None) == UNSUPPORTED
+    assert many(desc(n_rows=-1), 1, p, big, None) == INVALID
+    assert many(desc(nbr=None), 1, p, big, None) == INVALID
+    assert many(desc(order=None, tiled=256), 1, p, big, None) == INVALID       # a table needs an order
+    assert many(desc(prefix128=256), 1, p, big, None) == INVALID               # a prefix needs a table
+    assert many(desc(indice_pairs=256), 1, p, big, None) == INVALID            # pairs need counts
+    assert many(desc(indice_pairs=256, indice_num=256, ld=9), 1, p, big, None) == INVALID
+    assert many(desc(segtab=256), 1, p, big, None) == INVALID                  # segments need pairs
+    assert many(desc(kvol=31, n_rows=1 << 27, ld=1 << 27), 1, p, big, None) == RANGE
+
+
 def test_product_never_touches_the_oracle():
     """oracle/ is test infrastructure: nothing under msmdfusion_amd/ may import
     or call it, and the package has no CPU fallback branches."""

@@ -421,8 +421,8 @@ def test_rows_where_eq_many(dev):
 def _plan_tables(dev):
     """Tables of an index pass in miniature: SubM 3x3x3 of three sizes (one below a block, one
     a single row), both sides of a stride-2 conv (ld > rows: the output side is the shorter
-    one), a (3,1,1) conv (K = 3), a 2x2x2 conv (K = 8), a 3x3x2 SubM (K = 18: its key does
-    not fit under a table id -> the single-call path inside plan_many)."""
+    one), a (3,1,1) conv (K = 3), a 2x2x2 conv (K = 8), a 3x3x2 SubM (K = 18: its key leaves
+    no room for a table id -> a launch set of its own)."""
     from msmdfusion_amd import kernels as K
     shape = [11, 64, 64]
     tabs = []
@@ -497,6 +497,137 @@ def test_rulebook_plan_many_equals_the_single_plans(dev):
         assert torch.equal(r["prefix"][128], one["prefix"][128])
         assert torch.equal(r["pairs"][0], one["pairs"][0])
         assert torch.equal(r["pairs"][1], one["pairs"][1])
+
+
+# ---- a host oracle for a plan: numpy only, no library call on the expected side ----------
+# (csrc/tiling_key.hpp: kRank27; tests/test_boundary.py derives the table on its own)
+_RANK27 = np.array([19, 15, 20, 11, 5, 12, 21, 16, 22, 7, 3, 8, 1, 0,
+                    2, 9, 4, 10, 23, 17, 24, 13, 6, 14, 25, 18, 26], np.uint64)
+_SK_C1 = 12                                     # kSkC1Default, as test_tile_prefix takes it
+
+
+def _random_table(kvol, n, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.where(torch.rand(kvol, n, generator=g) < 0.35,
+                       torch.randint(0, max(n, 1), (kvol, n), generator=g), -1).int()
+
+
+def _oracle_pairs(nbr, ld):
+    """Ascending compaction per offset, -1 tails out to ld; the one-chunk segment table
+    [exclusive prefix of ceil(num / 32) (K + 1) | K zeros | num]."""
+    kvol = nbr.shape[0]
+    pairs = np.full((kvol, 2, ld), -1, np.int32)
+    num = np.zeros(kvol, np.int32)
+    for k in range(kvol):
+        rows = np.nonzero(nbr[k] >= 0)[0]
+        num[k] = rows.size
+        pairs[k, 0, :rows.size] = nbr[k, rows]
+        pairs[k, 1, :rows.size] = rows
+    steps = (num.astype(np.int64) + 31) // 32
+    seg = np.concatenate([[0], np.cumsum(steps), np.zeros(kvol, np.int64), num]).astype(np.int32)
+    return pairs, num, seg
+
+
+def _oracle_plan(nbr):
+    """order / tiled / both prefixes of nbr [K, n] (numpy int32), K <= 31."""
+    kvol, n = nbr.shape
+    act = nbr >= 0
+    bit = _RANK27 if kvol == 27 else np.arange(kvol, dtype=np.uint64)
+    key = (act.astype(np.uint64) << bit[:, None]).sum(0)
+    if kvol <= 15:
+        key |= (kvol - act.sum(0)).astype(np.uint64) << np.uint64(kvol)
+    order = np.argsort(key, kind="stable").astype(np.int32)
+    tiled = nbr[:, order]
+    prefix = {}
+    for rows in (128, 256):
+        w = []
+        for t0 in range(0, n, rows):
+            pos = np.minimum(np.arange(t0, t0 + rows), n - 1)       # past the end: the last row
+            groups = (tiled[:, pos] >= 0).reshape(kvol, rows // 32, 32).any(2).sum(1)
+            w.append(max(int((_SK_C1 + groups[groups > 0]).sum()), 1))
+        prefix[rows] = np.concatenate([[0], np.cumsum(w)]).astype(np.int32)
+    return dict(order=order, tiled=tiled, prefix=prefix)
+
+
+def _check_plan(res, want, pairs=None, what=""):
+    """A K.rulebook_plan / K.rulebook_plan_many result against the oracle, bit for bit."""
+    eq = lambda a, b: np.array_equal(a.cpu().numpy().reshape(-1), np.asarray(b).reshape(-1))
+    assert eq(res["order"], want["order"]), what
+    if res["tiled"] is not None:
+        assert eq(res["tiled"], want["tiled"]), what
+    for h, p in res["prefix"].items():
+        assert eq(p, want["prefix"][h]), (what, h)
+    if pairs is not None:
+        assert eq(res["pairs"][1], pairs[1]), what
+        assert eq(res["pairs"][0], pairs[0]), what
+        if res.get("segments") is not None:
+            assert res["segments"][1] == 1 and eq(res["segments"][0], pairs[2]), what
+
+
+@pytest.mark.parametrize("n", [1, 129, 2049])
+@pytest.mark.parametrize("kvol", [27, 3, 8, 18])
+def test_rulebook_plan_against_the_host_oracle(dev, kvol, n):
+    """msmd_rulebook_plan_many, msmd_rulebook_plan, msmd_rulebook_tiling and msmd_rulebook_pairs
+    against a numpy plan (the key of tiling_key.hpp, a stable argsort -- the radix sort is
+    stable, so the order itself is pinned --, the table in that order, the stream-K prefixes
+    of both tile heights, ascending pair lists with their -1 tails, the one-chunk segment
+    table).  Sizes across the tile heights and the 2048-entry scan tile; ld equal to the
+    table, a little longer, and past the padded table (the in-kernel -1 fill)."""
+    from msmdfusion_amd import kernels as K
+    host = _random_table(kvol, n, 1000 * kvol + n)
+    nbr = host.to(dev)
+    want = _oracle_plan(host.numpy())
+    lds = (n, n + 5, 2 * 2048 + 3)
+    everything = dict(tile_rows={128, 256}, want_pairs=True, want_segments=True)
+    res = K.rulebook_plan_many([dict(nbr=nbr, ld=ld, **everything) for ld in lds])
+    for ld, r in zip(lds, res):
+        pairs = _oracle_pairs(host.numpy(), ld)
+        assert r["tiled"] is not None and set(r["prefix"]) == {128, 256}
+        assert r["segments"] is not None
+        _check_plan(r, want, pairs, ("plan_many", ld))
+        one = K.rulebook_plan(nbr, tile_rows=(128, 256), want_pairs=True, ld=ld)
+        assert set(one["prefix"]) == {128, 256}
+        _check_plan(one, want, pairs, ("plan", ld))
+        got = K.rulebook_pairs(nbr, ld=ld)
+        assert np.array_equal(got[1].cpu().numpy(), pairs[1])
+        assert np.array_equal(got[0].cpu().numpy(), pairs[0]), ("pairs", ld)
+    order, tiled = K.rulebook_tiling(nbr)
+    assert np.array_equal(order.cpu().numpy(), want["order"])
+    assert np.array_equal(tiled.cpu().numpy(), want["tiled"])
+    only_order, none = K.rulebook_tiling(nbr, want_table=False)
+    assert none is None and np.array_equal(only_order.cpu().numpy(), want["order"])
+
+
+def test_rulebook_plan_many_mixed_groups_against_the_host_oracle(dev):
+    """One call with a K = 18 table (a 32-bit key: no room for a table id above it) between
+    two 3x3x3 tables, everything asked for; and a job list in which no table asks for a tiled
+    table or a prefix (pairs, segments, order only)."""
+    from msmdfusion_amd import kernels as K
+    hosts = [_random_table(27, 2049, 1), _random_table(18, 129, 2), _random_table(27, 129, 3)]
+    lds = [2049, 134, 2 * 2048 + 3]
+    jobs = [dict(nbr=h.to(dev), ld=ld, tile_rows={128, 256}, want_pairs=True, want_segments=True)
+            for h, ld in zip(hosts, lds)]
+    for h, ld, r in zip(hosts, lds, K.rulebook_plan_many(jobs)):
+        assert r["tiled"] is not None and set(r["prefix"]) == {128, 256}
+        assert r["segments"] is not None
+        _check_plan(r, _oracle_plan(h.numpy()), _oracle_pairs(h.numpy(), ld), h.shape)
+    wants = [dict(want_pairs=True), dict(want_segments=True), dict()]
+    jobs = [dict(nbr=h.to(dev), ld=ld, **w) for h, ld, w in zip(hosts, lds, wants)]
+    for h, ld, w, r in zip(hosts, lds, wants, K.rulebook_plan_many(jobs)):
+        assert r["tiled"] is None and not r["prefix"]
+        assert (r["pairs"] is None) == (not w) and (r["segments"] is None) == ("want_segments" not in w)
+        _check_plan(r, _oracle_plan(h.numpy()), _oracle_pairs(h.numpy(), ld) if w else None, h.shape)
+
+
+def test_rulebook_pairs_wide_kernel_against_the_host_oracle(dev):
+    """msmd_rulebook_pairs has no order, so no K <= 31 limit: a 5x5x5 table."""
+    from msmdfusion_amd import kernels as K
+    host = _random_table(125, 129, 125)
+    for ld in (129, 134, 2 * 2048 + 3):
+        pairs, num, _ = _oracle_pairs(host.numpy(), ld)
+        got = K.rulebook_pairs(host.to(dev), ld=ld)
+        assert np.array_equal(got[1].cpu().numpy(), num)
+        assert np.array_equal(got[0].cpu().numpy(), pairs), ld
 
 
 @pytest.mark.parametrize("cin,cout", [(64, 128), (32, 64), (80, 80), (128, 192), (40, 72),
