@@ -1795,6 +1795,80 @@ int msmd_vote_fusion_f32(const float* seeds /* [batch,num_seeds,3] */, int batch
                          float* feat /* [batch,5+num_classes+3,max_imvote*num_seeds] */,
                          uint8_t* mask /* [batch,max_imvote*num_seeds] */, msmd_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * f3-img  TransFusionHead's image stage (csrc/img_fusion.hip)
+ * replaces: the double loop over samples and views of TransFusionHead.forward_single
+ *           mmdet3d/models/dense_heads/transfusion_head.py:930-1004 -- the projection of the
+ *           queries and their box corners (:943-979), the on-image test and the host read of its
+ *           count (:981-987), centres, radius and sigma (:990-995), the [n, H W] Gaussian mask,
+ *           its threshold and logarithm (:996-999) and the masked attention they feed (:1003,
+ *           multi_head_attention_forward :286-504); LiDARInstance3DBoxes.corners
+ *           core/bbox/structures/lidar_box3d.py:46-84
+ *
+ * msmd_img_query_geometry_f32: one launch for the batch, the views looped inside.  pos3d
+ * [batch, 3, P] = (x, y, height) of the queries; boxes [batch, P, 7] = (x, y, z_bottom, dx, dy,
+ * dz, yaw); params [batch * V] in the layout of msmd_point_sample_params, m = lidar2img[view]
+ * times the reversed 3-D flow (or lidar2img[view] alone where the reference skips the flow).
+ * Per (sample, view, query), float32 without contraction: the eight corners in the reference's
+ * order; q = m [p 1], z = max(q.z, 1e-5), px = q.x / z * scale_x - crop_x (py likewise), flip:
+ * px = img_w - px; on = 0 < px < pad_w && 0 < py < pad_h (strict); pos = (px, py) / osf; centre =
+ * trunc(pos) (0 where not on); radius = ceil(|max - min of the corner pixels| / osf / 2),
+ * INT32_MAX where that is not below 2^31 or any corner pixel is NaN; sigma = (2 radius + 1) / 6.
+ * count [batch, V] = members of the view, valid = count > 1 (:985); winner [batch, P] = the
+ * highest valid view that sees the query or -1; mask = winner >= 0 (on_the_image_mask);
+ * win_pos / win_centre / win_sigma: the winner's values, 0 without one.  Every output element is
+ * written, nothing is read back.  P <= msmd_img_query_geometry_max_queries() (1024), V <=
+ * msmd_img_query_geometry_max_views() (8), else MSMD_ERR_UNSUPPORTED.
+ *
+ * msmd_gauss_attn_fwd_f32: q [batch * P, C] (projected, unscaled), k, v [batch * V, h * w, C]
+ * (projected), view [batch * P] (the row's view or -1), centre [batch * P, 2] (x, y), sigma
+ * [batch * P].  Per (row, head), d = C / heads, key j at cell (jx, jy) = (j % w, j / w):
+ *   arg_j = -((cx - jx)^2 + (cy - jy)^2) / (2 sigma^2)            (float32)
+ *   window = { j : expf(arg_j) >= FLT_EPSILON }
+ *   out = sum_window D_j softmax_window(q.k_j / sqrt(d) + arg_j) v_j,  lse = log sum exp
+ * Only the disc's bounding box, clipped to the map, is visited; the softmax is online.  A row
+ * with view -1 (or >= V) or an empty window gives out = 0, lse = 0.  Dropout 0 <= p < 1 on the
+ * weights: D_j = 0 where mix(seed, row, head, j) < floor(p 2^32), else 1 / (1 - p); p = 0: D = 1.
+ *   fmix(x): x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16
+ *   mix = fmix(fmix((fmix(lo(seed) ^ row * 0x9E3779B1) + head * 0x85EBCA77) ^ hi(seed))
+ *              ^ j * 0xC2B2AE3D)                                   (all uint32, wrapping)
+ * msmd_gauss_attn_bwd_f32: grad_q [batch * P, C], grad_k, grad_v [batch * V, h * w, C] (every
+ * element written), delta [batch * P, heads] (scratch: grad_out . out).  The mask is
+ * regenerated.  dQ is query-stationary; dK / dV key-stationary: a thread per key walks the
+ * sample's rows in ascending order, msmd_gauss_attn_row_chunk() rows per LDS round,
+ * msmd_gauss_attn_key_tile() keys per block.  No atomics; bitwise reproducible.
+ * Built: C / heads of 8, 16, 32 with C <= 256 (msmd_gauss_attn_supported), V <= 8; anything
+ * else MSMD_ERR_UNSUPPORTED.  h, w >= 1.
+ * ------------------------------------------------------------------------ */
+int msmd_img_query_geometry_max_queries(void);
+int msmd_img_query_geometry_max_views(void);
+int msmd_img_query_geometry_f32(const float* pos3d /* [batch,3,P] */,
+                                const float* boxes /* [batch,P,7] */,
+                                const msmd_point_sample_params* params /* [batch*V] */, int batch,
+                                int num_queries, int num_views, float out_size_factor_img,
+                                uint8_t* on /* [batch,V,P] */, float* pos /* [batch,V,P,2] */,
+                                int32_t* centre /* [batch,V,P,2] */,
+                                int32_t* radius /* [batch,V,P] */, float* sigma /* [batch,V,P] */,
+                                int32_t* count /* [batch,V] */, uint8_t* valid /* [batch,V] */,
+                                int32_t* winner /* [batch,P] */, uint8_t* mask /* [batch,P] */,
+                                float* win_pos /* [batch,P,2] */,
+                                int32_t* win_centre /* [batch,P,2] */,
+                                float* win_sigma /* [batch,P] */, msmd_stream_t stream);
+int msmd_gauss_attn_supported(int channels, int heads);
+int msmd_gauss_attn_key_tile(void);
+int msmd_gauss_attn_row_chunk(void);
+int msmd_gauss_attn_fwd_f32(const float* q, const float* k, const float* v, const int32_t* view,
+                            const int32_t* centre, const float* sigma, int batch, int num_queries,
+                            int num_views, int h, int w, int channels, int heads, float dropout,
+                            uint64_t seed, float* out /* [batch*P,C] */,
+                            float* lse /* [batch*P,heads] */, msmd_stream_t stream);
+int msmd_gauss_attn_bwd_f32(const float* q, const float* k, const float* v, const float* out,
+                            const float* grad_out, const float* lse, const int32_t* view,
+                            const int32_t* centre, const float* sigma, int batch, int num_queries,
+                            int num_views, int h, int w, int channels, int heads, float dropout,
+                            uint64_t seed, float* grad_q, float* grad_k, float* grad_v,
+                            float* delta /* [batch*P,heads] */, msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

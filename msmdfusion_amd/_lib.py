@@ -251,6 +251,14 @@ SIGNATURES = {
     "msmd_vote_fusion_max_k": (_i, []),
     "msmd_vote_fusion_f32": (_i, [_vp, _i, _i, _vp, _i, _vp, _ip, _vp, _i, _i, _vp, _i, _i, _vp, _vp,
                                   _vp]),
+    "msmd_img_query_geometry_max_queries": (_i, []),
+    "msmd_img_query_geometry_max_views": (_i, []),
+    "msmd_img_query_geometry_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _f] + [_vp] * 13),
+    "msmd_gauss_attn_supported": (_i, [_i, _i]),
+    "msmd_gauss_attn_key_tile": (_i, []),
+    "msmd_gauss_attn_row_chunk": (_i, []),
+    "msmd_gauss_attn_fwd_f32": (_i, [_vp] * 6 + [_i] * 7 + [_f, C.c_uint64, _vp, _vp, _vp]),
+    "msmd_gauss_attn_bwd_f32": (_i, [_vp] * 9 + [_i] * 7 + [_f, C.c_uint64] + [_vp] * 5),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

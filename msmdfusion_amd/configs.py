@@ -155,6 +155,34 @@ TRANSFUSION_PILLAR_L = dict(
     freeze_lidar_components=False)
 
 
+# configs/transfusion_nusc_voxel_LC.py and transfusion_nusc_pillar_LC.py: the L models with the
+# camera branch -- an image backbone and neck (injected here, their dicts kept as facts), and a
+# head with fuse_img=True over num_views = 6 views (msmdfusion_amd/fusion_head.py).  Equality
+# with the reference dicts is pinned by tests/golden/reference_transfusion_lc_configs.json.
+_LC_IMG_BRANCH = dict(
+    freeze_img=True,
+    img_backbone=dict(type="ResNet", depth=50, num_stages=4, out_indices=(0, 1, 2, 3),
+                      frozen_stages=1, norm_cfg=dict(type="BN", requires_grad=True),
+                      norm_eval=True, style="pytorch"),
+    img_neck=dict(type="FPN", in_channels=[256, 512, 1024, 2048], out_channels=256, num_outs=5))
+_LC_HEAD_IMG = dict(fuse_img=True, num_views=6, in_channels_img=256, out_size_factor_img=4)
+
+TRANSFUSION_VOXEL_LC = dict(
+    model=dict(TRANSFUSION_L["model"], **_LC_IMG_BRANCH,
+               pts_bbox_head=dict(_PTS_BBOX_HEAD, **_LC_HEAD_IMG),
+               train_cfg=dict(pts=_TRAIN_CFG_PTS), test_cfg=dict(pts=_TEST_CFG_PTS)),
+    samples_per_gpu=2, point_cloud_range=POINT_CLOUD_RANGE, voxel_size=VOXEL_SIZE,
+    optimizer=dict(type="AdamW", lr=0.0001, weight_decay=0.01),
+    freeze_lidar_components=True)
+
+TRANSFUSION_PILLAR_LC = dict(
+    model=dict(TRANSFUSION_PILLAR_L["model"], **_LC_IMG_BRANCH,
+               pts_bbox_head=dict(TRANSFUSION_PILLAR_L["model"]["pts_bbox_head"], **_LC_HEAD_IMG)),
+    samples_per_gpu=2, point_cloud_range=PILLAR_POINT_CLOUD_RANGE, voxel_size=PILLAR_VOXEL_SIZE,
+    optimizer=dict(type="AdamW", lr=0.0001, weight_decay=0.01),
+    freeze_lidar_components=True)
+
+
 # ---------------------------------------------------------------------------------------------
 # CenterPoint (configs/_base_/models/centerpoint_{01voxel,02pillar}_second_secfpn_nus.py under
 # configs/centerpoint/*): the `model` dicts after the `_base_` merge.  VOXEL: the 0.075 m
@@ -508,12 +536,18 @@ def build_head(cfg=None, rows=False):
     """pts_bbox_head of configs/MSMDFusion_nusc_voxel_LC.py:207-241 with its test_cfg
     (:260-268) and train_cfg (:242-259): TransFusionHead, LiDAR branch (msmdfusion_amd/head.py,
     head_loss.py).  cfg: one of the dicts above; one whose model carries `pts_bbox_head`,
-    `train_cfg` and `test_cfg` (TRANSFUSION_PILLAR_L) gets its own head."""
+    `train_cfg` and `test_cfg` (TRANSFUSION_PILLAR_L) gets its own head, and a head dict with
+    fuse_img=True (TRANSFUSION_VOXEL_LC, TRANSFUSION_PILLAR_LC) builds TransFusionHeadLC
+    (msmdfusion_amd/fusion_head.py)."""
     from .head import TransFusionHead
     if cfg is not None and "pts_bbox_head" in cfg.get("model", {}):
         # a config that carries its own head (TRANSFUSION_PILLAR_L): its dicts, not the LC ones
         m = cfg["model"]
         args = {k: v for k, v in m["pts_bbox_head"].items() if k != "type"}
+        if args.get("fuse_img"):
+            from .fusion_head import TransFusionHeadLC
+            return TransFusionHeadLC(test_cfg=dict(m["test_cfg"]["pts"]),
+                                     train_cfg=dict(m["train_cfg"]["pts"]), rows=rows, **args)
         return TransFusionHead(test_cfg=dict(m["test_cfg"]["pts"]),
                                train_cfg=dict(m["train_cfg"]["pts"]), rows=rows, **args)
     args = {k: v for k, v in _PTS_BBOX_HEAD.items() if k != "type"}

@@ -57,8 +57,12 @@ def _build_head(cfg, train_cfg, test_cfg, rows):
     if kind in ("CenterHead", "Anchor3DHead", "FreeAnchor3DHead"):
         from .registry import build_head
         return build_head(dict(cfg, train_cfg=pts(train_cfg), test_cfg=pts(test_cfg)))
-    if kind != "TransFusionHead":
+    if kind not in ("TransFusionHead", "TransFusionHeadLC"):
         raise KeyError("pts_bbox_head type %r is not built here" % kind)
+    if kind == "TransFusionHeadLC" or cfg.get("fuse_img"):
+        from .fusion_head import TransFusionHeadLC
+        return TransFusionHeadLC(train_cfg=pts(train_cfg), test_cfg=pts(test_cfg), rows=rows,
+                                 **args)
     return TransFusionHead(train_cfg=pts(train_cfg), test_cfg=pts(test_cfg), rows=rows, **args)
 
 
@@ -87,10 +91,16 @@ class TransFusionDetector(nn.Module):
         self.pts_neck = self._dense(pts_neck, build_neck, "SECONDFPNRows")
         self.pts_bbox_head = None if pts_bbox_head is None else \
             _build_head(pts_bbox_head, train_cfg, test_cfg, self.rows)
+        self.unused_cfg = dict(unused)      # keys of the config this path does not consume
+        # the image branch is injected as modules; a config dict for it (the LC configs carry
+        # the reference's ResNet / FPN dicts) is kept as a fact and builds nothing
+        if isinstance(img_backbone, dict):
+            self.unused_cfg["img_backbone"], img_backbone = img_backbone, None
+        if isinstance(img_neck, dict):
+            self.unused_cfg["img_neck"], img_neck = img_neck, None
         self.img_backbone, self.img_neck = img_backbone, img_neck
         self.freeze_img = freeze_img
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
-        self.unused_cfg = dict(unused)      # keys of the config this path does not consume
         if freeze_img:
             for m in (img_backbone, img_neck):
                 if isinstance(m, nn.Module):

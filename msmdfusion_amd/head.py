@@ -11,8 +11,9 @@ heads, and get_bboxes' score composition + box decoding, with the per-class-grou
 rotated NMS of `nms_type` through iou3d.nms_batched.
 The training half -- get_targets (HungarianAssigner3D, heat-map targets) and loss
 (:1051-1286) -- lives in msmdfusion_amd/head_loss.py and is reached through this class's
-`get_targets` / `loss`.  Not built: the image-fusion decoder stages (`fuse_img=True`), the
-HeuristicAssigner and NMS variants the configs do not use.
+`get_targets` / `loss`.  The image-fusion decoder stages (`fuse_img=True`) are the subclass
+TransFusionHeadLC in fusion_head.py.  Not built: the HeuristicAssigner and NMS variants the
+configs do not use.
 
 Parameter names and shapes are the reference's (`shared_conv.weight`,
 `heatmap_head.0.conv.weight`, `decoder.0.self_attn.in_proj_weight`,
@@ -201,8 +202,10 @@ class TransFusionHead(nn.Module):
                  loss_cls=None, loss_bbox=None, loss_heatmap=None, rows=False, **unused):
         super().__init__()
         if fuse_img:
-            raise NotImplementedError("TransFusionHead: the image-fusion stages are not built "
-                                      "(the LC config leaves fuse_img unset)")
+            raise NotImplementedError("TransFusionHead is the LiDAR branch; fuse_img=True is built "
+                                      "by TransFusionHeadLC (msmdfusion_amd/fusion_head.py), "
+                                      "which registry.build_head and configs.build_head pick "
+                                      "for such a config")
         if initialize_by_heatmap and learnable_query_pos:
             raise ValueError("initialized by heatmap is conflicting with learnable query position")
         self.num_classes, self.num_proposals, self.auxiliary = num_classes, num_proposals, auxiliary

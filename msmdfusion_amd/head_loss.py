@@ -668,8 +668,22 @@ def get_targets(head, gt_bboxes_3d, gt_labels_3d, preds_dict):
 
 def loss(head, gt_bboxes_3d, gt_labels_3d, preds_dicts):
     """TransFusionHead.loss (:1221-1286)."""
+    fuse_img = bool(getattr(head, "fuse_img", False))
+    if fuse_img and head.auxiliary and head.num_decoder_layers > 1:
+        raise NotImplementedError(
+            "TransFusionHead.loss: fuse_img=True returns the fused layer's result alone, and "
+            "with auxiliary=True and num_decoder_layers > 1 the reference slices that one "
+            "layer as if it held num_decoder_layers (:1250-1273): its own slicing is "
+            "ill-defined there, so this combination is refused")
     targets = get_targets(head, gt_bboxes_3d, gt_labels_3d, preds_dicts[0])
     labels, label_weights, bbox_targets, bbox_weights, ious, num_pos, matched_ious = targets[:7]
+    mask = getattr(head, "on_the_image_mask", None)
+    if mask is not None:                                                    # :1237-1240
+        label_weights = label_weights * mask
+        bbox_weights = bbox_weights * mask[:, :, None]
+        num_pos = bbox_weights.max(-1).values.sum()
+    # max(num_pos, 1): on a tensor without reading it back
+    avg = num_pos.clamp(min=1) if isinstance(num_pos, torch.Tensor) else max(num_pos, 1)
     pred = preds_dicts[0][0]
     losses = {}
     if head.initialize_by_heatmap:
@@ -684,13 +698,13 @@ def loss(head, gt_bboxes_3d, gt_labels_3d, preds_dicts):
         cls_score = pred["heatmap"][..., cut].permute(0, 2, 1).reshape(-1, head.num_classes)
         losses[prefix + "_loss_cls"] = head.loss_cls(
             cls_score, labels[..., cut].reshape(-1), label_weights[..., cut].reshape(-1),
-            avg_factor=max(num_pos, 1))
+            avg_factor=avg)
         parts = [pred[k][..., cut] for k in ("center", "height", "dim", "rot")]
         if "vel" in pred:
             parts.append(pred["vel"][..., cut])
         preds = torch.cat(parts, dim=1).permute(0, 2, 1)                    # [B, P, code]
         reg_w = bbox_weights[:, cut, :] * bbox_weights.new_tensor(code_weights)
         losses[prefix + "_loss_bbox"] = head.loss_bbox(preds, bbox_targets[:, cut, :], reg_w,
-                                                       avg_factor=max(num_pos, 1))
+                                                       avg_factor=avg)
     losses["matched_ious"] = matched_ious
     return losses

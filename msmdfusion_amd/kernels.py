@@ -3413,3 +3413,171 @@ def vote_fusion(seeds, boxes, box_offsets, box_offsets_host, imgs, params, num_c
                                    _p(params), classes, k, _p(feat), _p(mask), _stream()),
           "msmd_vote_fusion_f32")
     return feat, mask.view(torch.bool)
+
+
+# ------------------------------------------------------------------ TransFusionHead's image stage (csrc/img_fusion.hip)
+IMG_GEOMETRY_MAX_QUERIES = lib.msmd_img_query_geometry_max_queries()
+IMG_GEOMETRY_MAX_VIEWS = lib.msmd_img_query_geometry_max_views()
+IMG_GEOMETRY_PARAMS = 20        # floats of msmd_point_sample_params
+GAUSS_ATTN_KEY_TILE = lib.msmd_gauss_attn_key_tile()       # keys per block of the dK / dV pass
+GAUSS_ATTN_ROW_CHUNK = lib.msmd_gauss_attn_row_chunk()     # rows per LDS round of that pass
+
+
+class ImgQueryGeometry:
+    """What img_query_geometry leaves on the device (shapes in include/msmd_hip.h)."""
+    __slots__ = ("on", "pos", "centre", "radius", "sigma", "count", "valid", "winner", "mask",
+                 "win_pos", "win_centre", "win_sigma")
+
+
+def img_query_geometry(pos3d, boxes, params, out_size_factor_img):
+    """transfusion_head.py:943-995 and the bookkeeping of :985-987 / :1004-1006 for the whole
+    batch in one launch (msmd_img_query_geometry_f32).  pos3d float32 [B, 3, P]; boxes float32
+    [B, P, 7]; params float32 [B, V, 20] (msmd_point_sample_params per (sample, view))."""
+    _need_cuda(pos3d, boxes, params)
+    for t, what in ((pos3d, "pos3d"), (boxes, "boxes"), (params, "params")):
+        _need_dtype(t, torch.float32, what)
+    if pos3d.dim() != 3 or pos3d.shape[1] != 3 or not pos3d.is_contiguous():
+        raise ValueError("pos3d must be a contiguous float32 [B, 3, P] tensor, got %s"
+                         % (tuple(pos3d.shape),))
+    b, _, p = pos3d.shape
+    if tuple(boxes.shape) != (b, p, 7) or not boxes.is_contiguous():
+        raise ValueError("boxes must be a contiguous float32 [%d, %d, 7] tensor, got %s"
+                         % (b, p, tuple(boxes.shape)))
+    if params.dim() != 3 or params.shape[0] != b or params.shape[2] != IMG_GEOMETRY_PARAMS or \
+            not params.is_contiguous():
+        raise ValueError("params must be a contiguous float32 [%d, V, %d] tensor, got %s"
+                         % (b, IMG_GEOMETRY_PARAMS, tuple(params.shape)))
+    v = params.shape[1]
+    if not 1 <= v <= IMG_GEOMETRY_MAX_VIEWS:
+        raise ValueError("img_query_geometry: 1..%d views, got %d" % (IMG_GEOMETRY_MAX_VIEWS, v))
+    if p > IMG_GEOMETRY_MAX_QUERIES:
+        raise ValueError("img_query_geometry: at most %d queries, got %d"
+                         % (IMG_GEOMETRY_MAX_QUERIES, p))
+    if not float(out_size_factor_img) > 0:
+        raise ValueError("out_size_factor_img must be positive")
+    dev = pos3d.device
+
+    def new(shape, dtype):
+        return torch.empty(shape, dtype=dtype, device=dev)
+    g = ImgQueryGeometry()
+    g.on, g.pos = new((b, v, p), torch.uint8), new((b, v, p, 2), torch.float32)
+    g.centre, g.radius = new((b, v, p, 2), torch.int32), new((b, v, p), torch.int32)
+    g.sigma = new((b, v, p), torch.float32)
+    g.count, g.valid = new((b, v), torch.int32), new((b, v), torch.uint8)
+    g.winner, g.mask = new((b, p), torch.int32), new((b, p), torch.uint8)
+    g.win_pos, g.win_centre = new((b, p, 2), torch.float32), new((b, p, 2), torch.int32)
+    g.win_sigma = new((b, p), torch.float32)
+    check(lib.msmd_img_query_geometry_f32(
+        _p(pos3d), _p(boxes), _p(params), b, p, v, float(out_size_factor_img), _p(g.on), _p(g.pos),
+        _p(g.centre), _p(g.radius), _p(g.sigma), _p(g.count), _p(g.valid), _p(g.winner),
+        _p(g.mask), _p(g.win_pos), _p(g.win_centre), _p(g.win_sigma), _stream()),
+        "msmd_img_query_geometry_f32")
+    g.on, g.valid, g.mask = g.on.view(torch.bool), g.valid.view(torch.bool), g.mask.view(torch.bool)
+    return g
+
+
+def gauss_attn_supported(channels, heads):
+    """Whether the window-attention kernels are built for this width (C / heads of 8, 16, 32,
+    C <= 256)."""
+    return bool(lib.msmd_gauss_attn_supported(int(channels), int(heads)))
+
+
+def _gauss_attn_args(q, k, v, view, centre, sigma, num_views, h, w, heads, dropout):
+    _need_cuda(q, k, v, view, centre, sigma)
+    for t, what in ((q, "q"), (k, "k"), (v, "v"), (sigma, "sigma")):
+        _need_dtype(t, torch.float32, what)
+    _need_dtype(view, torch.int32, "view")
+    _need_dtype(centre, torch.int32, "centre")
+    if q.dim() != 2 or not q.is_contiguous():
+        raise ValueError("q must be a contiguous float32 [B P, C] tensor, got %s" % (tuple(q.shape),))
+    rows, c = q.shape
+    num_views, h, w, heads = int(num_views), int(h), int(w), int(heads)
+    if not gauss_attn_supported(c, heads):
+        raise ValueError("gauss_attn: C / heads must be 8, 16 or 32 with C <= 256, got %d / %d"
+                         % (c, heads))
+    if not 1 <= num_views <= IMG_GEOMETRY_MAX_VIEWS or h < 1 or w < 1:
+        raise ValueError("gauss_attn: 1..%d views and a map of at least 1 x 1, got V = %d, %d x %d"
+                         % (IMG_GEOMETRY_MAX_VIEWS, num_views, h, w))
+    if k.dim() != 3 or k.shape[1:] != (h * w, c) or k.shape[0] % num_views or \
+            k.shape != v.shape or not k.is_contiguous() or not v.is_contiguous():
+        raise ValueError("k and v must be contiguous float32 [B V, %d, %d] tensors, got %s and %s"
+                         % (h * w, c, tuple(k.shape), tuple(v.shape)))
+    batch = k.shape[0] // num_views
+    if batch == 0 or rows % batch:
+        raise ValueError("gauss_attn: %d rows do not divide over %d samples" % (rows, batch))
+    if tuple(view.shape) != (rows,) or tuple(centre.shape) != (rows, 2) or \
+            tuple(sigma.shape) != (rows,) or not view.is_contiguous() or \
+            not centre.is_contiguous() or not sigma.is_contiguous():
+        raise ValueError("view [R], centre [R, 2] and sigma [R] must be contiguous with R = %d"
+                         % rows)
+    if not 0.0 <= float(dropout) < 1.0:
+        raise ValueError("dropout must be in [0, 1), got %r" % (dropout,))
+    for t, what in ((q, "q"), (k, "k"), (v, "v")):
+        if t.data_ptr() % 16:
+            raise ValueError("gauss_attn: %s must start on a 16-byte boundary (the kernels load "
+                             "four floats at a time)" % what)
+    return batch, rows // batch, c
+
+
+def _aligned16(t):
+    """t contiguous and on a 16-byte boundary (a copy where a view is not)."""
+    t = t.contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def gauss_attn_forward(q, k, v, view, centre, sigma, num_views, h, w, heads, dropout=0.0, seed=0):
+    """msmd_gauss_attn_fwd_f32 -> (out [B P, C], lse [B P, heads])."""
+    batch, p, c = _gauss_attn_args(q, k, v, view, centre, sigma, num_views, h, w, heads, dropout)
+    out = torch.empty_like(q)
+    lse = torch.empty((q.shape[0], int(heads)), dtype=torch.float32, device=q.device)
+    check(lib.msmd_gauss_attn_fwd_f32(_p(q), _p(k), _p(v), _p(view), _p(centre), _p(sigma), batch,
+                                      p, int(num_views), int(h), int(w), c, int(heads),
+                                      float(dropout), int(seed) & (2 ** 64 - 1), _p(out), _p(lse),
+                                      _stream()), "msmd_gauss_attn_fwd_f32")
+    return out, lse
+
+
+def gauss_attn_backward(q, k, v, out, grad_out, lse, view, centre, sigma, num_views, h, w, heads,
+                        dropout=0.0, seed=0):
+    """msmd_gauss_attn_bwd_f32 -> (grad_q, grad_k, grad_v); the dropout mask is regenerated."""
+    batch, p, c = _gauss_attn_args(q, k, v, view, centre, sigma, num_views, h, w, heads, dropout)
+    _need_cuda(out, grad_out, lse)
+    for t, what in ((out, "out"), (grad_out, "grad_out"), (lse, "lse")):
+        _need_dtype(t, torch.float32, what)
+    if out.shape != q.shape or grad_out.shape != q.shape or not out.is_contiguous() or \
+            not grad_out.is_contiguous() or tuple(lse.shape) != (q.shape[0], int(heads)) or \
+            not lse.is_contiguous():
+        raise ValueError("out and grad_out must be contiguous like q, lse [R, heads]")
+    if out.data_ptr() % 16 or grad_out.data_ptr() % 16:
+        raise ValueError("gauss_attn: out and grad_out must start on a 16-byte boundary")
+    gq, gk, gv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    delta = torch.empty_like(lse)
+    check(lib.msmd_gauss_attn_bwd_f32(_p(q), _p(k), _p(v), _p(out), _p(grad_out), _p(lse), _p(view),
+                                      _p(centre), _p(sigma), batch, p, int(num_views), int(h),
+                                      int(w), c, int(heads), float(dropout),
+                                      int(seed) & (2 ** 64 - 1), _p(gq), _p(gk), _p(gv), _p(delta),
+                                      _stream()), "msmd_gauss_attn_bwd_f32")
+    return gq, gk, gv
+
+
+class _GaussAttn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, view, centre, sigma, num_views, h, w, heads, dropout, seed):
+        q, k, v = _aligned16(q), _aligned16(k), _aligned16(v)
+        out, lse = gauss_attn_forward(q, k, v, view, centre, sigma, num_views, h, w, heads,
+                                      dropout, seed)
+        ctx.save_for_backward(q, k, v, out, lse, view, centre, sigma)
+        ctx.args = (num_views, h, w, heads, dropout, seed)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        q, k, v, out, lse, view, centre, sigma = ctx.saved_tensors
+        gq, gk, gv = gauss_attn_backward(q, k, v, out, _aligned16(grad_out), lse, view, centre,
+                                         sigma, *ctx.args)
+        return (gq, gk, gv) + (None,) * 9
+
+
+def gauss_attn(q, k, v, view, centre, sigma, num_views, h, w, heads, dropout=0.0, seed=0):
+    """Gaussian-window cross-attention with autograd (q, k, v); see gauss_attn_forward."""
+    return _GaussAttn.apply(q, k, v, view, centre, sigma, num_views, h, w, heads, dropout, seed)
