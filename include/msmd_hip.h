@@ -1869,6 +1869,90 @@ int msmd_gauss_attn_bwd_f32(const float* q, const float* k, const float* v, cons
                             uint64_t seed, float* grad_q, float* grad_k, float* grad_v,
                             float* delta /* [batch*P,heads] */, msmd_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * n7  H3DNet primitive targets (csrc/primitive.hip)
+ * replaces: PrimitiveHead.get_targets_single and its helpers
+ *           mmdet3d/models/roi_heads/mask_heads/primitive_head.py:327-601 (the loop over the
+ *           instances of a sample, with its nonzero, unique and ~14 host reads per instance),
+ *           match_point2line :676-715, match_point2plane :717-733, point2line_dist :657-674,
+ *           _assign_primitive_line_targets :803-866, _assign_primitive_surface_targets
+ *           :868-950, _get_plane_fomulation :952-967, check_horizon / check_dist :631-655
+ *
+ * Sample s owns point rows point_offsets[s] .. point_offsets[s+1] and box rows
+ * box_offsets[s] .. box_offsets[s+1] (device int32 arrays, as msmd_vote_targets_f32 takes
+ * them).  Boxes are their eight corners in DepthBoxes.corners order.
+ *
+ * msmd_primitive_index (mode independent; the three heads of a step share one): a point is
+ * foreground when sem != num_classes; the instances of a sample are the distinct instance
+ * labels of its foreground points in ascending order, rank = position in that order
+ * (torch.unique).  The index holds, per (sample, rank), the number of points, the lowest
+ * foreground point (its sem is the instance's class: pts_semantic_mask[indices][0]) and the
+ * instance's points in ascending point order.  DEVIATION: labels outside [0, label_bound) take
+ * no part (the reference accepts any label); label_bound <= msmd_primitive_max_labels() (1024).
+ * max_points and max_instances are host-known bounds that only size grids.
+ *
+ * msmd_primitive_targets_f32: mode 0 = 'z' (num_dims 2), 1 = 'xy' (num_dims 1), 2 = 'line'
+ * (num_dims 0).  One workgroup per (sample, instance) sweeps the instance's list three times in
+ * steps of msmd_primitive_point_chunk() entries: minima, then counts / moments / sums, then
+ * decisions and writes.  Per instance, all float32 and rounded one operation at a time:
+ *   box = corners[rank] -- the RANK, not the label: the reference indexes with its enumerate
+ *     counter (:376-383).  DEVIATION: an instance whose rank is not below the sample's box count
+ *     (the reference raises IndexError) gets no targets.
+ *   planes (n, d): lower (0, 0, 1, -corners[7].z); upper (0, 0, 1, -mean z of corners 1, 2, 5,
+ *     6); left = cross(c2 - c3, c3 - c0) through c0, divided by its norm; right: that normal,
+ *     d = -mean(n . c) over corners 4, 5, 7, 6; front = cross(c0 - c4, c4 - c5) through c5;
+ *     back: that normal over corners 3, 2, 7, 6.
+ *   DEVIATION: where the reference raises NotImplementedError (check_horizon, check_dist, a
+ *     normal's z not below lower_thresh -- none can fire for a finite box rotated about z, the
+ *     normals' z components are exactly 0) the instance gets no targets; a degenerate or NaN box
+ *     fails these comparisons and so gets none either.
+ *   plane matching: dist = |p . n + d|; selected = |dist - min over the instance| < dist_thresh;
+ *     the minimum is torch.min's (a NaN distance is the minimum, then nothing is selected).
+ *   surfaces (modes z, xy): on when count(selected) > num_point and the unbiased variance of
+ *     dist[selected] < var_thresh; the variance is accumulated in double, pivoted on the
+ *     minimum, from the float32 distances.
+ *   lines (mode line) are matched among the plane's selected points: with_yaw, point2line_dist
+ *     in its own form sqrt(|a2p|^2 - length^2) < line_thresh (a negative radicand is NaN and
+ *     selects nothing); else |x - xmin|, |x - xmax|, |y - ymin|, |y - ymax| < line_thresh.  A
+ *     line is on when count > num_point_line.
+ *   centres and sizes: every branch of the two _assign_* helpers (both yaw forms, center_axises
+ *     [1,1,0,0] and [2,2], the left / right calls on point2line_matching[2:]).  Means over
+ *     selected points are double sums in a fixed order over the instance's list, rounded to
+ *     float32 once.
+ *   write order: line: 4 bottom, 4 top, 2 left, 2 right; z: bottom, top; xy: left, right, front,
+ *     back.  A later primitive overwrites point_offset / point_sem of a point an earlier one
+ *     wrote, point_mask is the OR: each lane evaluates its own point in that order.  No atomics
+ *     on outputs, no write races, bitwise reproducible.
+ * point_mask [total_points], point_offset [total_points, 3], point_sem [total_points, 3 +
+ * num_dims + 1] (centre, sizes, class as float): every row the offsets cover is written, rows
+ * the reference leaves untouched as zeros.  Nothing is read back.
+ * Null pointers, negative counts, label_bound outside 1 .. 1024, an unknown mode, num_dims not
+ * matching the mode and a too-small index return MSMD_ERR_INVALID_ARG.
+ * ------------------------------------------------------------------------ */
+int msmd_primitive_max_labels(void);  /* largest label_bound */
+int msmd_primitive_point_chunk(void); /* list entries per sweep step */
+size_t msmd_primitive_index_workspace_bytes(int num_samples, int total_points, int label_bound);
+int msmd_primitive_index(const int64_t* pts_semantic_mask /* [total_points] */,
+                         const int64_t* pts_instance_mask /* [total_points] */,
+                         const int32_t* point_offsets /* [num_samples+1] */, int num_samples,
+                         int total_points, int max_points, int num_classes, int label_bound,
+                         int max_instances, void* index, size_t index_bytes,
+                         msmd_stream_t stream);
+int msmd_primitive_targets_f32(const float* points /* [total_points,ld] */, int ld,
+                               const int64_t* pts_semantic_mask /* [total_points] */,
+                               const int32_t* point_offsets /* [num_samples+1] */,
+                               const float* corners /* [total_boxes,8,3] */,
+                               const int32_t* box_offsets /* [num_samples+1] */, int num_samples,
+                               int total_points, int total_boxes, int max_points, int max_boxes,
+                               int with_yaw, int mode, int num_dims, float dist_thresh,
+                               float var_thresh, float lower_thresh, int num_point,
+                               int num_point_line, float line_thresh, int label_bound,
+                               const void* index, size_t index_bytes,
+                               float* point_mask /* [total_points] */,
+                               float* point_offset /* [total_points,3] */,
+                               float* point_sem /* [total_points,3+num_dims+1] */,
+                               msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

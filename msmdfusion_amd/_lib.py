@@ -259,6 +259,12 @@ SIGNATURES = {
     "msmd_gauss_attn_row_chunk": (_i, []),
     "msmd_gauss_attn_fwd_f32": (_i, [_vp] * 6 + [_i] * 7 + [_f, C.c_uint64, _vp, _vp, _vp]),
     "msmd_gauss_attn_bwd_f32": (_i, [_vp] * 9 + [_i] * 7 + [_f, C.c_uint64] + [_vp] * 5),
+    "msmd_primitive_max_labels": (_i, []),
+    "msmd_primitive_point_chunk": (_i, []),
+    "msmd_primitive_index_workspace_bytes": (_sz, [_i, _i, _i]),
+    "msmd_primitive_index": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "msmd_primitive_targets_f32": (_i, [_vp, _i, _vp, _vp, _vp, _vp] + [_i] * 8 + [_f, _f, _f, _i,
+                                        _i, _f, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -663,3 +663,46 @@ MVXNET_DV_SECOND_KITTI = dict(
     pts_bbox_head=dict(_kitti_anchor_head(512, 40.0), assigner_per_size=True,
                        assign_per_class=True),
     train_cfg=dict(pts=_MVX_TRAIN), test_cfg=dict(pts=_MVX_TEST))
+
+
+# ------------------------------------------------------------------------------- H3DNet (front)
+# configs/_base_/models/h3dnet.py: the four-stream backbone and the three primitive heads of
+# the ScanNet model (the RoI head that consumes them is not built yet)
+H3DNET_SCANNET_BACKBONE = dict(
+    type="MultiBackbone", num_streams=4, suffixes=["net0", "net1", "net2", "net3"],
+    conv_cfg=dict(type="Conv1d"), norm_cfg=dict(type="BN1d", eps=1e-5, momentum=0.01),
+    act_cfg=dict(type="ReLU"),
+    backbones=dict(
+        type="PointNet2SASSG", in_channels=4, num_points=(2048, 1024, 512, 256),
+        radius=(0.2, 0.4, 0.8, 1.2), num_samples=(64, 32, 16, 16),
+        sa_channels=((64, 64, 128), (128, 128, 256), (128, 128, 256), (128, 128, 256)),
+        fp_channels=((256, 256), (256, 256)), norm_cfg=dict(type="BN2d"),
+        sa_cfg=dict(type="PointSAModule", pool_mod="max", use_xyz=True, normalize_xyz=True)))
+
+
+def _h3dnet_primitive(mode, num_dims, side_weight, sem_weight):
+    chamfer = dict(type="ChamferDistance", mode="l1", reduction="sum",
+                   loss_src_weight=side_weight, loss_dst_weight=side_weight)
+    return dict(
+        type="PrimitiveHead", num_dims=num_dims, num_classes=18, primitive_mode=mode,
+        upper_thresh=100.0, surface_thresh=0.5,
+        vote_module_cfg=dict(
+            in_channels=256, vote_per_seed=1, gt_per_seed=1, conv_channels=(256, 256),
+            conv_cfg=dict(type="Conv1d"), norm_cfg=dict(type="BN1d"), norm_feats=True,
+            vote_loss=dict(type="ChamferDistance", mode="l1", reduction="none",
+                           loss_dst_weight=10.0)),
+        vote_aggregation_cfg=dict(
+            type="PointSAModule", num_point=1024, radius=0.3, num_sample=16,
+            mlp_channels=[256, 128, 128, 128], use_xyz=True, normalize_xyz=True),
+        feat_channels=(128, 128), conv_cfg=dict(type="Conv1d"), norm_cfg=dict(type="BN1d"),
+        objectness_loss=dict(type="CrossEntropyLoss", class_weight=[0.4, 0.6], reduction="mean",
+                             loss_weight=30.0),
+        center_loss=dict(chamfer), semantic_reg_loss=dict(chamfer),
+        semantic_cls_loss=dict(type="CrossEntropyLoss", reduction="sum", loss_weight=sem_weight),
+        train_cfg=dict(dist_thresh=0.2, var_thresh=1e-2, lower_thresh=1e-6, num_point=100,
+                       num_point_line=10, line_thresh=0.2))
+
+
+H3DNET_PRIMITIVE_Z = _h3dnet_primitive("z", 2, 0.5, 1.0)
+H3DNET_PRIMITIVE_XY = _h3dnet_primitive("xy", 1, 0.5, 1.0)
+H3DNET_PRIMITIVE_LINE = _h3dnet_primitive("line", 0, 1.0, 2.0)

@@ -202,9 +202,10 @@ class DepthBoxes:
         """[G, 8, 3] in the order of depth_box3d.py:46-84: the unit cube's corners about the
         bottom centre, scaled, turned about z by the yaw, moved."""
         dims = self.dims
-        unit = dims.new_tensor([[0, 0, 0], [0, 0, 1], [0, 1, 1], [0, 1, 0],
+        # (_constant, not new_tensor: PrimitiveHead's targets call this and must not block)
+        unit = _constant(dims, [[0, 0, 0], [0, 0, 1], [0, 1, 1], [0, 1, 0],
                                 [1, 0, 0], [1, 0, 1], [1, 1, 1], [1, 1, 0]])
-        unit = unit - dims.new_tensor([0.5, 0.5, 0])
+        unit = unit - _constant(dims, [0.5, 0.5, 0])
         corners = dims.view([-1, 1, 3]) * unit.reshape([1, 8, 3])
         rot_sin, rot_cos = torch.sin(self.tensor[:, 6]), torch.cos(self.tensor[:, 6])
         ones, zeros = torch.ones_like(rot_cos), torch.zeros_like(rot_cos)

@@ -3581,3 +3581,96 @@ class _GaussAttn(torch.autograd.Function):
 def gauss_attn(q, k, v, view, centre, sigma, num_views, h, w, heads, dropout=0.0, seed=0):
     """Gaussian-window cross-attention with autograd (q, k, v); see gauss_attn_forward."""
     return _GaussAttn.apply(q, k, v, view, centre, sigma, num_views, h, w, heads, dropout, seed)
+
+
+# ------------------------------------------------------------------ H3DNet primitive targets
+PRIMITIVE_MODES = {"z": 0, "xy": 1, "line": 2}
+PRIMITIVE_NUM_DIMS = {"z": 2, "xy": 1, "line": 0}
+# labels outside [0, label_bound) take no part (a deviation from the reference, which accepts
+# any label); the default is the library's limit, msmd_primitive_max_labels()
+PRIMITIVE_MAX_LABELS = 1024
+
+
+def _primitive_offsets(point_offsets, total):
+    _need_dtype(point_offsets, torch.int32, "offsets")
+    samples = point_offsets.numel() - 1
+    if samples < 0 or point_offsets.dim() != 1 or not point_offsets.is_contiguous():
+        raise ValueError("offsets hold S + 1 contiguous int32 entries")
+    return samples
+
+
+def primitive_index(pts_semantic_mask, pts_instance_mask, point_offsets, num_classes,
+                    label_bound=None, max_points=None, max_instances=None):
+    """The mode-independent index of msmd_primitive_targets_f32 for a batch: the instances of
+    every sample (distinct instance labels of the points with sem != num_classes, ascending),
+    their class point and their points in ascending order.  Masks long [P], sample s = rows
+    point_offsets[s] .. point_offsets[s+1] (int32 [S + 1] on the device).  Labels outside
+    [0, label_bound) take no part; label_bound defaults to PRIMITIVE_MAX_LABELS.  max_points /
+    max_instances: host-known bounds that size grids only.  -> an opaque uint8 tensor; build it
+    once per step and hand it to the three heads."""
+    _need_cuda(pts_semantic_mask, pts_instance_mask, point_offsets)
+    total = pts_semantic_mask.numel()
+    for t, what in ((pts_semantic_mask, "pts_semantic_mask"),
+                    (pts_instance_mask, "pts_instance_mask")):
+        _need_dtype(t, torch.long, what)
+        if t.dim() != 1 or t.numel() != total or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous long [P] tensor" % what)
+    samples = _primitive_offsets(point_offsets, total)
+    bound = PRIMITIVE_MAX_LABELS if label_bound is None else int(label_bound)
+    nbytes = lib.msmd_primitive_index_workspace_bytes(samples, total, bound)
+    if nbytes == 0:
+        raise ValueError("primitive_index: label_bound must be in 1 .. %d" % PRIMITIVE_MAX_LABELS)
+    index = torch.empty((nbytes,), dtype=torch.uint8, device=pts_semantic_mask.device)
+    check(lib.msmd_primitive_index(_p(pts_semantic_mask), _p(pts_instance_mask),
+                                   _p(point_offsets), samples, total,
+                                   total if max_points is None else int(max_points),
+                                   int(num_classes), bound,
+                                   bound if max_instances is None else int(max_instances),
+                                   _p(index), nbytes, _stream()), "msmd_primitive_index")
+    return index
+
+
+def primitive_targets(points, pts_semantic_mask, point_offsets, corners, box_offsets, index, mode,
+                      with_yaw, train_cfg, label_bound=None, max_points=None, max_boxes=None):
+    """PrimitiveHead.get_targets_single for every sample in one launch, nothing read back.
+    points float32 [P, >= 3]; corners float32 [T, 8, 3] in DepthBoxes.corners order with
+    box_offsets like point_offsets; index from primitive_index (same offsets and label_bound);
+    mode 'z' | 'xy' | 'line'; train_cfg holds dist_thresh, var_thresh, lower_thresh, num_point,
+    num_point_line, line_thresh.  The box of an instance is corners[rank of its label], as in
+    the reference.  -> (point_mask float32 [P], point_offset [P, 3], point_sem
+    [P, 3 + num_dims + 1])."""
+    _need_cuda(points, pts_semantic_mask, point_offsets, corners, box_offsets, index)
+    _need_dtype(points, torch.float32, "points")
+    _need_dtype(corners, torch.float32, "corners")
+    _need_dtype(pts_semantic_mask, torch.long, "pts_semantic_mask")
+    _need_dtype(index, torch.uint8, "index")
+    if points.dim() != 2 or points.shape[1] < 3 or not points.is_contiguous():
+        raise ValueError("points must be a contiguous float32 [P, >= 3] tensor")
+    if corners.dim() != 3 or tuple(corners.shape[1:]) != (8, 3) or not corners.is_contiguous():
+        raise ValueError("corners must be a contiguous float32 [T, 8, 3] tensor")
+    total = points.shape[0]
+    if pts_semantic_mask.dim() != 1 or pts_semantic_mask.numel() != total or \
+            not pts_semantic_mask.is_contiguous():
+        raise ValueError("pts_semantic_mask must be a contiguous long [P] tensor")
+    if mode not in PRIMITIVE_MODES:
+        raise ValueError("primitive mode must be one of 'z', 'xy', 'line'")
+    samples = _primitive_offsets(point_offsets, total)
+    if _primitive_offsets(box_offsets, corners.shape[0]) != samples:
+        raise ValueError("point_offsets and box_offsets hold S + 1 entries each")
+    bound = PRIMITIVE_MAX_LABELS if label_bound is None else int(label_bound)
+    dims = PRIMITIVE_NUM_DIMS[mode]
+    dev = points.device
+    mask = torch.empty((total,), dtype=torch.float32, device=dev)
+    offset = torch.empty((total, 3), dtype=torch.float32, device=dev)
+    sem = torch.empty((total, 4 + dims), dtype=torch.float32, device=dev)
+    check(lib.msmd_primitive_targets_f32(
+        _p(points), points.shape[1], _p(pts_semantic_mask), _p(point_offsets), _p(corners),
+        _p(box_offsets), samples, total, corners.shape[0],
+        total if max_points is None else int(max_points),
+        corners.shape[0] if max_boxes is None else int(max_boxes), 1 if with_yaw else 0,
+        PRIMITIVE_MODES[mode], dims, float(train_cfg["dist_thresh"]),
+        float(train_cfg["var_thresh"]), float(train_cfg["lower_thresh"]),
+        int(train_cfg["num_point"]), int(train_cfg["num_point_line"]),
+        float(train_cfg["line_thresh"]), bound, _p(index), index.numel(), _p(mask), _p(offset),
+        _p(sem), _stream()), "msmd_primitive_targets_f32")
+    return mask, offset, sem

@@ -1,7 +1,10 @@
-"""PointNet++ backbones: PointNet2SASSG (single-scale grouping, with feature propagation) and
-PointNet2SAMSG (multi-scale grouping), with the constructor arguments, output dict keys and
-index bookkeeping of mmdet3d/models/backbones/pointnet2_sa_{ssg,msg}.py and
+"""PointNet++ backbones: PointNet2SASSG (single-scale grouping, with feature propagation),
+PointNet2SAMSG (multi-scale grouping) and H3DNet's MultiBackbone (several SSG streams and an
+aggregation MLP), with the constructor arguments, output dict keys and index bookkeeping of
+mmdet3d/models/backbones/{pointnet2_sa_ssg,pointnet2_sa_msg,multi_backbone}.py and
 base_pointnet.py.  auto_fp16 of the reference is plain float32 here."""
+import copy
+
 import torch
 from torch import nn
 
@@ -74,13 +77,21 @@ class PointNet2SASSG(BasePointNet):
                 fp_source_channel = cur_fp_mlps[-1]
                 fp_target_channel = skip_channel_list.pop()
 
-    def forward(self, points):
+    def forward(self, points, sa_indices=None, return_sa_indices=False):
         """points (B, N, 3 + C) -> dict(fp_xyz, fp_features, fp_indices), lists over the FP
-        stages; fp_indices index the input points."""
+        stages; fp_indices index the input points.  sa_indices (not in the reference): one
+        (B, num_points[i]) int32 tensor per SA level, used instead of sampling there --
+        MultiBackbone hands the first stream's samples to the others.  return_sa_indices adds
+        the per-level samples this pass used to the dict (key `sa_level_indices`)."""
         xyz, features = self._split_point_feats(points)
+        given = sa_indices
+        assert given is None or len(given) == self.num_sa
+        level_indices = []
         sa_xyz, sa_features, sa_indices = [xyz], [features], [_input_indices(xyz)]
         for i in range(self.num_sa):
-            cur_xyz, cur_features, cur_indices = self.SA_modules[i](sa_xyz[i], sa_features[i])
+            cur_xyz, cur_features, cur_indices = self.SA_modules[i](
+                sa_xyz[i], sa_features[i], indices=None if given is None else given[i])
+            level_indices.append(cur_indices)
             sa_xyz.append(cur_xyz)
             sa_features.append(cur_features)
             sa_indices.append(torch.gather(sa_indices[-1], 1, cur_indices.long()))
@@ -91,7 +102,21 @@ class PointNet2SASSG(BasePointNet):
                 sa_features[self.num_sa - i - 1], fp_features[-1]))
             fp_xyz.append(sa_xyz[self.num_sa - i - 1])
             fp_indices.append(sa_indices[self.num_sa - i - 1])
-        return dict(fp_xyz=fp_xyz, fp_features=fp_features, fp_indices=fp_indices)
+        ret = dict(fp_xyz=fp_xyz, fp_features=fp_features, fp_indices=fp_indices)
+        if return_sa_indices:
+            ret["sa_level_indices"] = level_indices
+        return ret
+
+    def shares_sampling_with(self, other):
+        """True when `other` samples what this backbone samples at every SA level: D-FPS reads
+        only xyz, the levels' inputs are the previous levels' samples, so equal num_points on
+        equal input points give equal indices."""
+        def plan(net):
+            return [(tuple(m.num_point), tuple(m.fps_mod_list), tuple(m.fps_sample_range_list))
+                    for m in net.SA_modules]
+        return type(other) is PointNet2SASSG and type(self) is PointNet2SASSG and \
+            plan(self) == plan(other) and \
+            all(mods == ("D-FPS",) and ranges == (-1,) for _, mods, ranges in plan(self))
 
 
 @BACKBONES.register_module()
@@ -158,3 +183,75 @@ class PointNet2SAMSG(BasePointNet):
                 out_sa_features.append(sa_features[-1])
                 out_sa_indices.append(sa_indices[-1])
         return dict(sa_xyz=out_sa_xyz, sa_features=out_sa_features, sa_indices=out_sa_indices)
+
+
+@BACKBONES.register_module()
+class MultiBackbone(nn.Module):
+    """multi_backbone.py:10-124: `num_streams` backbones on the same points and an aggregation
+    MLP over their last FP features (`hd_feature`); the streams' dict keys get the suffixes.
+
+    share_sampling (not in the reference): all streams receive the same points and D-FPS reads
+    only xyz, so streams with equal `num_points` compute the same sampling indices at every SA
+    level.  Stream 0 samples; every later PointNet2SASSG stream that samples the same way takes
+    its indices (`sa_indices=`) instead of running furthest-point sampling again.  The results
+    are equal bit for bit; streams that do not qualify sample on their own."""
+
+    def __init__(self, num_streams, backbones, aggregation_mlp_channels=None,
+                 conv_cfg=dict(type="Conv1d"), norm_cfg=dict(type="BN1d", eps=1e-5, momentum=0.01),
+                 act_cfg=dict(type="ReLU"), suffixes=("net0", "net1"), share_sampling=True,
+                 **kwargs):
+        super().__init__()
+        assert isinstance(backbones, dict) or isinstance(backbones, list)
+        if isinstance(backbones, dict):
+            backbones = [copy.deepcopy(backbones) for _ in range(num_streams)]
+        assert len(backbones) == num_streams
+        assert len(suffixes) == num_streams
+        assert conv_cfg["type"] == "Conv1d" and act_cfg["type"] == "ReLU"
+        self.backbone_list = nn.ModuleList()
+        self.suffixes = suffixes
+        self.share_sampling = share_sampling
+        out_channels = 0
+        for backbone_cfg in backbones:
+            out_channels += backbone_cfg["fp_channels"][-1][-1]
+            self.backbone_list.append(BACKBONES.build(backbone_cfg))
+        if aggregation_mlp_channels is None:
+            aggregation_mlp_channels = [out_channels, out_channels // 2,
+                                        out_channels // len(self.backbone_list)]
+        else:
+            aggregation_mlp_channels.insert(0, out_channels)    # in place, as the reference
+        norm_kwargs = dict(norm_cfg)
+        norm = norm_kwargs.pop("type")
+        norm_kwargs.pop("requires_grad", None)
+        self.aggregation_layers = nn.Sequential()
+        for i in range(len(aggregation_mlp_channels) - 1):
+            self.aggregation_layers.add_module(
+                f"layer{i}", ConvModule(aggregation_mlp_channels[i],
+                                        aggregation_mlp_channels[i + 1], 1, padding=0, bias=True,
+                                        conv="Conv1d", norm=norm, norm_kwargs=norm_kwargs))
+
+    def init_weights(self, pretrained=None):
+        if isinstance(pretrained, str):
+            state = torch.load(pretrained, map_location="cpu")
+            self.load_state_dict(state.get("state_dict", state), strict=False)
+
+    def forward(self, points):
+        """points (B, N, 3 + C) -> the streams' dicts with suffixed keys (fp_xyz_net0, ...) and
+        hd_feature (B, C_out, num_seeds)."""
+        ret, fp_features, shared = {}, [], None
+        first = self.backbone_list[0]
+        for ind, backbone in enumerate(self.backbone_list):
+            if not self.share_sampling or not isinstance(first, PointNet2SASSG) or \
+                    not first.shares_sampling_with(backbone):
+                cur_ret = backbone(points)
+            elif ind == 0:
+                cur_ret = backbone(points, return_sa_indices=True)
+                shared = cur_ret.pop("sa_level_indices")
+            else:
+                cur_ret = backbone(points, sa_indices=shared)
+            cur_suffix = self.suffixes[ind]
+            fp_features.append(cur_ret["fp_features"][-1])
+            if cur_suffix != "":
+                cur_ret = {k + "_" + cur_suffix: v for k, v in cur_ret.items()}
+            ret.update(cur_ret)
+        ret["hd_feature"] = self.aggregation_layers(torch.cat(fp_features, dim=1))
+        return ret
