@@ -81,8 +81,13 @@ int msmd_hard_voxelize(const float* points, int num_points, int num_features,
 /* The same for SEVERAL clouds in one launch set (the B LiDAR sweeps of a batch and the
  * virtual points of its four image scales: MSMDFusion.py:462-491 calls the voxel layer once
  * per sample and scale, each call its own voxel size): blocks find their cloud, the scan
- * restarts per cloud, one fill initialises every cloud's tables.  Results per cloud as
- * msmd_hard_voxelize's, bit for bit.  The workspace is shared by the descriptors of a call. */
+ * restarts per cloud, one fill initialises every cloud's tables.  msmd_hard_voxelize is the
+ * one-descriptor case of this call: the same kernels, a workspace of
+ * msmd_voxelize_workspace_bytes (for an empty cloud, which only has *voxel_num = 0 written,
+ * that is one 256-byte unit whatever max_voxels is).  The workspace is shared by the descriptors of a call.
+ * Every descriptor, then the workspace (against the largest launch set of 12 clouds), is
+ * checked before the first fill or launch: a call that returns an error has enqueued nothing
+ * and leaves every output untouched. */
 typedef struct msmd_voxelize_desc {
   const float* points;             /* [num_points, num_features] */
   int32_t num_points, num_features;
@@ -274,11 +279,15 @@ int msmd_rulebook_subm3d_bitmap(const int32_t* indices, int n, int batch_size,
                                 int32_t* nbr, void* workspace, size_t workspace_bytes,
                                 msmd_stream_t stream);
 
-/* msmd_rulebook_subm3d / _bitmap for MANY voxel sets in one launch set (2 fills + at most 6
+/* msmd_rulebook_subm3d / _bitmap for MANY voxel sets in one launch set (2 fills + at most 7
  * kernels whatever the number of tables): an index pass builds the SubM tables of all its
  * voxel sets together at its end -- nothing in the index chain reads one.  descs: HOST
- * array; method 0 = hash index, 1 = occupancy bitmap (as the single calls); tables with
- * n = 0 are skipped.  Results identical to the single calls. */
+ * array; method 0 = hash index, 1 = occupancy bitmap; tables with n = 0 are skipped.
+ * msmd_rulebook_subm3d (method 0) and msmd_rulebook_subm3d_bitmap (method 1) are the
+ * one-descriptor case of this call: the same kernels, their *_workspace_bytes the size of
+ * that one descriptor.  Every descriptor, then the workspace (against the largest launch set
+ * of 16 tables), is checked before the first fill or launch: a call that returns an error
+ * has enqueued nothing and leaves every table untouched. */
 typedef struct msmd_subm_desc {
   const int32_t* indices;      /* [n,4] (b,z,y,x) */
   int32_t n, batch_size;
@@ -1037,7 +1046,8 @@ int msmd_rows_where_eq(const int32_t* flags, int stride, int n, int value, int64
                        msmd_stream_t stream);
 /* The same for n_lists (flag vector, value) pairs in one scan: the only-3D and only-2D row lists
  * of all four image scales of a step (host arrays of n_lists pointers / ints).  Per list as
- * msmd_rows_where_eq, the -1 tail included; a list of capacity 0 is skipped. */
+ * msmd_rows_where_eq, the -1 tail included; a list of capacity 0 is skipped.  Every list is
+ * checked before the first launch: a call that returns an error has enqueued nothing. */
 size_t msmd_rows_where_eq_many_workspace_bytes(const int* lens, int n_lists);
 int msmd_rows_where_eq_many(const int32_t* const* flags, const int* strides, const int* lens,
                             const int* values, int64_t* const* rows, const int* capacities,

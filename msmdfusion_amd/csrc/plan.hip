@@ -43,16 +43,10 @@ struct PlanTab {
   msmd_plan_desc d[kPlanMax];
 };
 
-__device__ __forceinline__ int table_of(const int* __restrict__ first, int n, int b) {
-  int s = 0;
-  while (s + 1 < n && b >= first[s + 1]) ++s;     // uniform: scalar loads of kernel arguments
-  return s;
-}
-
 __global__ __launch_bounds__(256) void keys_many_kernel(const PlanTab tab,
                                                         uint32_t* __restrict__ keys,
                                                         int32_t* __restrict__ vals) {
-  const int s = table_of(tab.blk0, tab.n, blockIdx.x);
+  const int s = segment_of(tab.blk0, tab.n, blockIdx.x);
   const msmd_plan_desc& d = tab.d[s];
   const int o = (blockIdx.x - tab.blk0[s]) * 256 + threadIdx.x;
   if (o >= d.n_rows) return;
@@ -68,7 +62,7 @@ __global__ __launch_bounds__(256) void keys_many_kernel(const PlanTab tab,
 // order[p] = the row at tile position p; tiled[k][p] = nbr[k][order[p]]
 __global__ __launch_bounds__(256) void finish_many_kernel(const PlanTab tab,
                                                           const int32_t* __restrict__ sorted) {
-  const int s = table_of(tab.blk0, tab.n, blockIdx.x);
+  const int s = segment_of(tab.blk0, tab.n, blockIdx.x);
   const msmd_plan_desc& d = tab.d[s];
   const int p = (blockIdx.x - tab.blk0[s]) * 256 + threadIdx.x;
   const int n = d.n_rows;
@@ -95,7 +89,7 @@ __global__ __launch_bounds__(256) void tile_weight_many_kernel(const PlanTab tab
   const int vt = blockIdx.x * 4 + (threadIdx.x >> 6);        // tile of this wave
   if (vt >= n_tiles) return;
   const int lane = threadIdx.x & 63;
-  const int s = table_of(tab.tile0, tab.n, vt);
+  const int s = segment_of(tab.tile0, tab.n, vt);
   const msmd_plan_desc& d = tab.d[s];
   const int n = d.n_rows, kvol = d.kvol;
   int t = vt - tab.tile0[s];
@@ -142,7 +136,7 @@ __global__ __launch_bounds__(1024) void tile_prefix_many_kernel(const PlanTab ta
 __global__ __launch_bounds__(kScanBlock) void pair_sums_many_kernel(const PlanTab tab,
                                                                     int* __restrict__ tile_sums) {
   __shared__ int smem[kScanBlock / 64];
-  const int s = table_of(tab.pblk0, tab.n, blockIdx.x);
+  const int s = segment_of(tab.pblk0, tab.n, blockIdx.x);
   const msmd_plan_desc& d = tab.d[s];
   const int n = d.n_rows;
   const int tpk = (n + kScanTile - 1) / kScanTile;
@@ -176,7 +170,7 @@ __global__ __launch_bounds__(kScanBlock) void pair_sums_many_kernel(const PlanTa
 __global__ __launch_bounds__(kScanBlock) void pairs_apply_many_kernel(
     const PlanTab tab, const int* __restrict__ tile_sums_all) {
   __shared__ int smem[kScanSmem];
-  const int s = table_of(tab.pblk0, tab.n, blockIdx.x);
+  const int s = segment_of(tab.pblk0, tab.n, blockIdx.x);
   const msmd_plan_desc& d = tab.d[s];
   const int n_rows = d.n_rows, ld = d.ld;
   const int tpk = (n_rows + kScanTile - 1) / kScanTile, rows_pad = tpk * kScanTile;

@@ -26,6 +26,8 @@
 
 #include <stdlib.h>
 
+#include <algorithm>
+
 namespace msmd {
 namespace {
 
@@ -36,35 +38,6 @@ struct Geom {
 };
 
 // ---------------------------------------------------------------- SubM ----
-__global__ __launch_bounds__(256) void subm_insert(const int32_t* __restrict__ idx, int n,
-                                                   Geom g, unsigned long long* table, int bits) {
-  int j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= n) return;
-  int4 r = ((const int4*)idx)[j];
-  // duplicate coordinates: the CPU reference's grid keeps the LAST row
-  // (geometry.h:277-282) -> keep max(row)
-  hash_insert<true>(table, bits, cell_id(r.x, r.y, r.z, r.w, g.shape), (uint32_t)j);
-}
-
-// thread (o, k): blockIdx.y = kernel offset -> stores of one block are
-// contiguous in nbr[k][*]; the 16-B index row load is coalesced.
-__global__ __launch_bounds__(256) void subm_lookup(const int32_t* __restrict__ idx, int n, Geom g,
-                                                   const unsigned long long* __restrict__ table,
-                                                   int bits, int32_t* __restrict__ nbr) {
-  int o = blockIdx.x * 256 + threadIdx.x;
-  if (o >= n) return;
-  const int k = blockIdx.y;
-  const int kx = k % g.ks[2], ky = (k / g.ks[2]) % g.ks[1], kz = k / (g.ks[2] * g.ks[1]);
-  int4 r = ((const int4*)idx)[o];
-  // pair (in, out) sits under offset k when out = in + pad - k (stride 1,
-  // geometry.h:40-44,69): the input of output o is at o - pad + k.
-  int z = r.y - g.pd[0] + kz, y = r.z - g.pd[1] + ky, x = r.w - g.pd[2] + kx;
-  int v = -1;
-  if (z >= 0 && z < g.shape[0] && y >= 0 && y < g.shape[1] && x >= 0 && x < g.shape[2])
-    v = hash_find(table, bits, cell_id(r.x, z, y, x, g.shape));
-  nbr[(size_t)k * n + o] = v;
-}
-
 // SubM through an occupancy bitmap of the INPUT grid (large voxel sets).  The hash above
 // costs one random 8-byte slot read per (row, offset): 27 sector fetches per voxel, 3.5 % of
 // HBM peak on algorithmic bytes at 720 k voxels.  With one bit per cell the three
@@ -81,7 +54,7 @@ __global__ __launch_bounds__(256) void subm_lookup(const int32_t* __restrict__ i
 // (`used`, 1/256 byte per cell: 3 MB for the 765 M-cell stress grid against the fine bitmap's
 // 95.6 MB) says whether the block holds a voxel.  Only `used` is cleared; every voxel stores
 // 1 into its block's byte and zeros into the block's 32-byte sector (plain idempotent
-// stores, subm_bm_mark_blocks), a second pass sets the fine bits, the counting passes read a
+// stores, subm_insert_many), a second pass sets the fine bits, the counting passes read a
 // sector only where the byte is set and store a prefix only for occupied blocks, and a
 // look-up tests the byte first.  At the stress size that removes ~300 MB of traffic (clear +
 // two counting reads of the bitmap + the prefix of every block) from a job whose algorithmic
@@ -95,7 +68,7 @@ constexpr int kBmBlockWords = 8;
 // order -- bit = (z & 3) << 6 | (y & 7) << 3 | (x & 7), so the cells of an x line inside a
 // brick share one word.  A voxel's 3x3x3 neighbourhood lies in 2.3 bricks on average (at most
 // 8) instead of in 9 different sectors of a row-major bitmap, and one thread resolves all of
-// a voxel's offsets out of them (subm_bm_lookup).  The rank order is the brick order: any
+// a voxel's offsets out of them (subm_bm_lookup_many).  The rank order is the brick order: any
 // fixed order serves, rank -> row goes through rank2row.
 struct BmDims {
   int tz, ty, tx;
@@ -164,39 +137,6 @@ __device__ __forceinline__ int bm_rank(const uint32_t* __restrict__ bits,
 #pragma unroll
   for (uint32_t w = 0; w < (uint32_t)kBmBlockWords; ++w) r += w < in_blk ? __popc(ws[w]) : 0;
   return r;
-}
-
-// pass 1: the block's byte and a cleared sector (every voxel of a block stores the same values)
-__global__ __launch_bounds__(256) void subm_bm_mark_blocks(const int32_t* __restrict__ idx, int n,
-                                                           Geom g, uint8_t* used, uint32_t* bits) {
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= n) return;
-  const int4 r = ((const int4*)idx)[j];
-  const uint32_t blk = bm_cell(r.x, r.y, r.z, r.w, g.shape) >> 8;
-  used[blk] = 1;
-  uint4* line = (uint4*)(bits + (size_t)blk * kBmBlockWords);
-  line[0] = make_uint4(0, 0, 0, 0);
-  line[1] = make_uint4(0, 0, 0, 0);
-}
-// pass 2 (a launch of its own: every sector is cleared before any fine bit is set)
-__global__ __launch_bounds__(256) void subm_bm_mark(const int32_t* __restrict__ idx, int n, Geom g,
-                                                    uint32_t* bits) {
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= n) return;
-  const int4 r = ((const int4*)idx)[j];
-  bitmap_set(bits, bm_cell(r.x, r.y, r.z, r.w, g.shape));
-}
-
-// rank -> row; duplicate coordinates keep the LAST row, as the hash and the CPU grid do
-__global__ __launch_bounds__(256) void subm_bm_rows(const int32_t* __restrict__ idx, int n, Geom g,
-                                                    const uint32_t* __restrict__ bits,
-                                                    const int* __restrict__ block_prefix,
-                                                    int32_t* rank2row) {
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= n) return;
-  const int4 r = ((const int4*)idx)[j];
-  const uint32_t c = bm_cell(r.x, r.y, r.z, r.w, g.shape);
-  atomicMax(&rank2row[bm_rank(bits, block_prefix, c, bits[c >> 5])], j);
 }
 
 // All offsets of output row o by one thread (the bricks of its neighbourhood stay in the
@@ -318,19 +258,6 @@ __device__ __forceinline__ void bm_lookup_row(const int4 r, int o, int n, const 
     bm_lookup_plane<3, 3>(r, o, n, g, bits, used, block_prefix, rank2row, nbr, kz);
   else
     bm_lookup_plane_any(r, o, n, g, bits, used, block_prefix, rank2row, nbr, kz);
-}
-
-__global__ __launch_bounds__(256) void subm_bm_lookup(const int32_t* __restrict__ idx, int n, Geom g,
-                                                      const uint32_t* __restrict__ bits,
-                                                      const uint8_t* __restrict__ coarse,
-                                                      const int* __restrict__ block_prefix,
-                                                      const int32_t* __restrict__ rank2row,
-                                                      int32_t* __restrict__ nbr) {
-  const int o = blockIdx.x * 256 + threadIdx.x;
-  if (o >= n) return;
-  // blockIdx.y = the kz plane
-  bm_lookup_row(((const int4*)idx)[o], o, n, g, bits, coarse, block_prefix, rank2row, nbr,
-                blockIdx.y);
 }
 
 // ------------------------------------------------------------- strided ----
@@ -516,114 +443,11 @@ int check_geom(const int* shape, const int* ks, const int* st, const int* pd, in
 using namespace msmd;
 
 // ------------------------------------------------------------------ SubM ---
-MSMD_EXPORT size_t msmd_rulebook_subm_workspace_bytes(int n) {
-  int bits = next_pow2_bits(2L * (n > 0 ? n : 1));
-  if (bits < 6) bits = 6;
-  return align_up(sizeof(unsigned long long) << bits);
-}
-
-MSMD_EXPORT int msmd_rulebook_subm3d(const int32_t* indices, int n, int batch_size,
-                                     const int* spatial_shape, const int* ksize, int32_t* nbr,
-                                     void* workspace, size_t workspace_bytes,
-                                     msmd_stream_t stream) {
-  Geom g;
-  int rc = check_geom(spatial_shape, ksize, nullptr, nullptr, batch_size, &g);
-  if (rc) return rc;
-  if (n < 0 || (n > 0 && (!indices || !nbr))) return MSMD_ERR_INVALID_ARG;
-  if (n == 0) return MSMD_OK;
-  int bits = next_pow2_bits(2L * n);
-  if (bits < 6) bits = 6;
-  if (workspace_bytes < (sizeof(unsigned long long) << bits) || ((uintptr_t)workspace & 255))
-    return MSMD_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  auto* table = (unsigned long long*)workspace;
-  hipMemsetAsync(table, 0xFF, sizeof(unsigned long long) << bits, st);
-  const int nb = ceil_div(n, 256);
-  MSMD_LAUNCH(subm_insert, dim3(nb), dim3(256), 0, st, indices, n, g, table, bits);
-  MSMD_LAUNCH(subm_lookup, dim3(nb, g.kvol), dim3(256), 0, st, indices, n, g, table, bits,
-                     nbr);
-  return launch_status();
-}
-
-namespace {
-struct SubmBmWs {
-  uint32_t* bits;
-  uint8_t* coarse;              // one byte per block
-  size_t coarse_bytes;
-  int* block_prefix;
-  int* tiles;
-  int* total;
-  int32_t* rank2row;
-  size_t nwords, nblocks;
-};
-template <typename A>
-void carve_subm_bm(A& a, SubmBmWs* w, int n, int batch, const int* shape) {
-  const size_t nblocks = bm_blocks(batch, shape);
-  const size_t nwords = nblocks * kBmBlockWords;
-  uint32_t* bits = a.template take<uint32_t>(nwords);
-  const size_t cw = nblocks;
-  uint8_t* coarse = a.template take<uint8_t>(cw);
-  int* prefix = a.template take<int>(nblocks);
-  int* tiles = a.template take<int>(scan_num_tiles((long)nblocks) + 1);
-  int* total = a.template take<int>(1);
-  int32_t* rows = a.template take<int32_t>(n > 0 ? n : 1);
-  if (w) *w = SubmBmWs{bits, coarse, cw, prefix, tiles, total, rows, nwords, nblocks};
-}
-}  // namespace
-
-MSMD_EXPORT size_t msmd_rulebook_subm_bitmap_workspace_bytes(int n, int batch_size,
-                                                             const int* spatial_shape) {
-  if (n < 0 || batch_size < 1 || !spatial_shape) return 0;
-  ArenaSize a;
-  carve_subm_bm(a, (SubmBmWs*)nullptr, n, batch_size, spatial_shape);
-  return a.off;
-}
-
-MSMD_EXPORT int msmd_rulebook_subm3d_bitmap(const int32_t* indices, int n, int batch_size,
-                                            const int* spatial_shape, const int* ksize,
-                                            int32_t* nbr, void* workspace,
-                                            size_t workspace_bytes, msmd_stream_t stream) {
-  Geom g;
-  int rc = check_geom(spatial_shape, ksize, nullptr, nullptr, batch_size, &g);
-  if (rc) return rc;
-  if (n < 0 || (n > 0 && (!indices || !nbr))) return MSMD_ERR_INVALID_ARG;
-  if (n == 0) return MSMD_OK;
-  if (bm_blocks(batch_size, spatial_shape) >= (1u << 24)) return MSMD_ERR_RANGE;  // brick << 8 | bit
-  Arena a(workspace, workspace_bytes);
-  SubmBmWs w;
-  carve_subm_bm(a, &w, n, batch_size, spatial_shape);
-  if (!a.ok()) return MSMD_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const bool flags = bm_use_flags(w.nblocks, n);
-  const uint8_t* used = flags ? w.coarse : nullptr;
-  if (flags)
-    hipMemsetAsync(w.coarse, 0, w.coarse_bytes, st);
-  else
-    hipMemsetAsync(w.bits, 0, sizeof(uint32_t) * w.nwords, st);
-  hipMemsetAsync(w.rank2row, 0xFF, sizeof(int32_t) * (size_t)n, st);
-  const int nb = ceil_div(n, 256);
-  if (flags)
-    MSMD_LAUNCH(subm_bm_mark_blocks, dim3(nb), dim3(256), 0, st, indices, n, g, w.coarse, w.bits);
-  MSMD_LAUNCH(subm_bm_mark, dim3(nb), dim3(256), 0, st, indices, n, g, w.bits);
-  device_scan(BmBlockCount{w.bits, used}, StoreUsedPrefix{w.block_prefix}, (int)w.nblocks,
-              w.tiles, w.total, -1, st);
-  MSMD_LAUNCH(subm_bm_rows, dim3(nb), dim3(256), 0, st, indices, n, g, (const uint32_t*)w.bits,
-              (const int*)w.block_prefix, w.rank2row);
-  // a thread per (row, kz plane): 152 against 163 us at the stress size, 46 against 55 at the
-  // nominal one, with one thread per row (27 dependent look-ups in a row)
-  MSMD_LAUNCH(subm_bm_lookup, dim3(nb, g.ks[0]), dim3(256), 0, st, indices, n, g,
-              (const uint32_t*)w.bits, used, (const int*)w.block_prefix,
-              (const int32_t*)w.rank2row, nbr);
-  return launch_status();
-}
-
-// ------------------------------------------------- SubM, many tables --------
 // The SubM tables of an index pass in one launch set (msmd_rulebook_subm3d_many).  Like the
 // plans (plan.hip) nothing in the index chain reads a SubM table -- the feature pass and
 // the planning do -- so the ~12 tables of an LC step are built together at the end of
-// prepare(): 2 fills + 6 kernels instead of 3 (hash index) or 10 (bitmap index) launches
-// each.  Per table the same index structure and the same kernels' arithmetic as the single
-// calls; results identical.
+// prepare(): 2 fills + 7 kernels instead of 3 (hash index) or 8 (bitmap index) launches
+// each.  msmd_rulebook_subm3d and _bitmap are launch sets of one table.
 namespace {
 
 constexpr int kSubmMax = 16;      // tables per launch set
@@ -639,26 +463,37 @@ struct SubmJob {
   Geom g;
   int n, hbits, nblocks, pad;
 };
+// The launch table, a kernel argument.  N = kSubmMax, or 1 for a call with one table: that
+// call's blocks need no look-up of their table (segment_of) in front of the loads of its
+// fields -- 1.4 us of a 34.5 us call at 75 k voxels (hash index: two kernels of about one wave
+// round each, where that latency shows; the 0.14 KB argument in place of 2.3 KB alone: nothing).
+template <int N>
 struct SubmTab {
   int n;
-  int blk0[kSubmMax + 1];       // first 256-row block of table s
-  int sblk0[kSubmMax + 1];      // first scan tile of table s's bitmap blocks
-  SubmJob j[kSubmMax];
+  int blk0[N + 1];              // first 256-row block of table s
+  int sblk0[N + 1];             // first scan tile of table s's bitmap blocks
+  SubmJob j[N];
+  // the block prefixes of the bitmap-indexed tables as a segmented scan (scan.hpp); a
+  // hash-indexed table is a segment of no tiles
+  __device__ const auto& seg_tile0() const { return sblk0; }
+  __device__ int seg_len(int s) const { return j[s].nblocks; }
+  __device__ BmBlockCount seg_count(int s) const { return {j[s].bits, j[s].coarse}; }
+  __device__ StoreUsedPrefix seg_emit(int s) const { return {j[s].block_prefix}; }
+  __device__ void seg_done(int, int) const {}
 };
 
-__device__ __forceinline__ int subm_table_of(const int* __restrict__ first, int n, int b) {
-  int s = 0;
-  while (s + 1 < n && b >= first[s + 1]) ++s;
-  return s;
-}
-
-__global__ __launch_bounds__(256) void subm_insert_many(const SubmTab tab) {
-  const int s = subm_table_of(tab.blk0, tab.n, blockIdx.x);
+// hash index: insert; bitmap index, pass 1: the bit, or -- with block flags -- the block's
+// byte and a cleared sector (every voxel of a block stores the same values)
+template <typename Tab>
+__global__ __launch_bounds__(256) void subm_insert_many(const Tab tab) {
+  const int s = segment_of(tab.blk0, tab.n, blockIdx.x);
   const SubmJob& J = tab.j[s];
   const int j = (blockIdx.x - tab.blk0[s]) * 256 + threadIdx.x;
   if (j >= J.n) return;
   const int4 r = ((const int4*)J.idx)[j];
   if (J.table) {
+    // duplicate coordinates: the CPU reference's grid keeps the LAST row
+    // (geometry.h:277-282) -> keep max(row)
     hash_insert<true>(J.table, J.hbits, cell_id(r.x, r.y, r.z, r.w, J.g.shape), (uint32_t)j);
     return;
   }
@@ -667,15 +502,18 @@ __global__ __launch_bounds__(256) void subm_insert_many(const SubmTab tab) {
     bitmap_set(J.bits, c);
     return;
   }
-  const uint32_t blk = c >> 8;    // (subm_bm_mark_blocks)
+  const uint32_t blk = c >> 8;
   J.coarse[blk] = 1;
   uint4* line = (uint4*)(J.bits + (size_t)blk * kBmBlockWords);
   line[0] = make_uint4(0, 0, 0, 0);
   line[1] = make_uint4(0, 0, 0, 0);
 }
 
-__global__ __launch_bounds__(256) void subm_bm_mark_many(const SubmTab tab) {
-  const int s = subm_table_of(tab.blk0, tab.n, blockIdx.x);
+// pass 2 of the flag scheme (a launch of its own: every sector is cleared before any fine bit
+// is set)
+template <typename Tab>
+__global__ __launch_bounds__(256) void subm_bm_mark_many(const Tab tab) {
+  const int s = segment_of(tab.blk0, tab.n, blockIdx.x);
   const SubmJob& J = tab.j[s];
   if (!J.coarse) return;          // (hash index, or bits set by the first pass)
   const int j = (blockIdx.x - tab.blk0[s]) * 256 + threadIdx.x;
@@ -684,53 +522,10 @@ __global__ __launch_bounds__(256) void subm_bm_mark_many(const SubmTab tab) {
   bitmap_set(J.bits, bm_cell(r.x, r.y, r.z, r.w, J.g.shape));
 }
 
-__global__ __launch_bounds__(kScanBlock) void subm_bm_sums_many(const SubmTab tab,
-                                                               int* __restrict__ tile_sums) {
-  __shared__ int smem[kScanBlock / 64];
-  const int s = subm_table_of(tab.sblk0, tab.n, blockIdx.x);
-  const SubmJob& J = tab.j[s];
-  const BmBlockCount count{J.bits, J.coarse};
-  const int base = (blockIdx.x - tab.sblk0[s]) * kScanTile;
-  int c = 0;
-#pragma unroll
-  for (int q = 0; q < kScanItems; ++q) {
-    const int i = base + q * kScanBlock + threadIdx.x;
-    if (i < J.nblocks) c += count(i);
-  }
-  c = wave_sum(c);
-  if ((threadIdx.x & 63) == 0) smem[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int t = 0;
-    for (int i = 0; i < kScanBlock / 64; ++i) t += smem[i];
-    tile_sums[blockIdx.x] = t;
-  }
-}
-
-__global__ __launch_bounds__(kScanBlock) void subm_bm_prefix_many(
-    const SubmTab tab, const int* __restrict__ tile_sums) {
-  __shared__ int smem[kScanSmem];
-  const int s = subm_table_of(tab.sblk0, tab.n, blockIdx.x);
-  const SubmJob& J = tab.j[s];
-  const BmBlockCount count{J.bits, J.coarse};
-  const int base = (blockIdx.x - tab.sblk0[s]) * kScanTile;
-  int v[kScanItems], ex[kScanItems];
-#pragma unroll
-  for (int q = 0; q < kScanItems; ++q) {
-    const int i = base + q * kScanBlock + threadIdx.x;
-    v[q] = i < J.nblocks ? count(i) : 0;
-  }
-  const int carry = block_range_sum<kScanBlock>(tile_sums, tab.sblk0[s], (int)blockIdx.x, smem);
-  tile_excl_scan(v, ex, smem);
-#pragma unroll
-  for (int q = 0; q < kScanItems; ++q) {
-    const int i = base + q * kScanBlock + threadIdx.x;
-    if (v[q]) J.block_prefix[i] = carry + ex[q];       // (occupied blocks only)
-  }
-}
-
-__global__ __launch_bounds__(256) void subm_bm_rows_many(const SubmTab tab) {
-  const int s = subm_table_of(tab.blk0, tab.n, blockIdx.x);
+// rank -> row; duplicate coordinates keep the LAST row, as the hash and the CPU grid do
+template <typename Tab>
+__global__ __launch_bounds__(256) void subm_bm_rows_many(const Tab tab) {
+  const int s = segment_of(tab.blk0, tab.n, blockIdx.x);
   const SubmJob& J = tab.j[s];
   if (!J.bits) return;
   const int j = (blockIdx.x - tab.blk0[s]) * 256 + threadIdx.x;
@@ -740,27 +535,39 @@ __global__ __launch_bounds__(256) void subm_bm_rows_many(const SubmTab tab) {
   atomicMax(&J.rank2row[bm_rank(J.bits, J.block_prefix, c, J.bits[c >> 5])], j);
 }
 
-// blockIdx.y: the offset k (hash index) or the kz plane (bitmap index)
-__global__ __launch_bounds__(256) void subm_lookup_many(const SubmTab tab) {
-  const int s = subm_table_of(tab.blk0, tab.n, blockIdx.x);
+// The look-up of the hash-indexed tables.  blockIdx.y: the offset k -- stores of one block are
+// contiguous in nbr[k][*]; the 16-B index row load is coalesced.  (A kernel of its own: with the
+// bitmap look-up in the same kernel a one-table call at 75 k voxels took 0.3 us longer.)
+template <typename Tab>
+__global__ __launch_bounds__(256) void subm_hash_lookup_many(const Tab tab) {
+  const int s = segment_of(tab.blk0, tab.n, blockIdx.x);
   const SubmJob& J = tab.j[s];
   const Geom& g = J.g;
   const int o = (blockIdx.x - tab.blk0[s]) * 256 + threadIdx.x;
-  const int n = J.n;
-  if (o >= n || (!J.table && (int)blockIdx.y >= g.ks[0])) return;   // bitmap index: y = kz plane
+  const int n = J.n, k = blockIdx.y;
+  if (!J.table || o >= n || k >= g.kvol) return;
   const int4 r = ((const int4*)J.idx)[o];
-  if (J.table) {
-    const int k = blockIdx.y;
-    if (k >= g.kvol) return;
-    const int kx = k % g.ks[2], ky = (k / g.ks[2]) % g.ks[1], kz = k / (g.ks[2] * g.ks[1]);
-    const int z = r.y - g.pd[0] + kz, y = r.z - g.pd[1] + ky, x = r.w - g.pd[2] + kx;
-    int v = -1;
-    if (z >= 0 && z < g.shape[0] && y >= 0 && y < g.shape[1] && x >= 0 && x < g.shape[2])
-      v = hash_find(J.table, J.hbits, cell_id(r.x, z, y, x, g.shape));
-    J.nbr[(size_t)k * n + o] = v;
-    return;
-  }
-  bm_lookup_row(r, o, n, g, J.bits, J.coarse, J.block_prefix, J.rank2row, J.nbr, blockIdx.y);
+  const int kx = k % g.ks[2], ky = (k / g.ks[2]) % g.ks[1], kz = k / (g.ks[2] * g.ks[1]);
+  // pair (in, out) sits under offset k when out = in + pad - k (stride 1,
+  // geometry.h:40-44,69): the input of output o is at o - pad + k.
+  const int z = r.y - g.pd[0] + kz, y = r.z - g.pd[1] + ky, x = r.w - g.pd[2] + kx;
+  int v = -1;
+  if (z >= 0 && z < g.shape[0] && y >= 0 && y < g.shape[1] && x >= 0 && x < g.shape[2])
+    v = hash_find(J.table, J.hbits, cell_id(r.x, z, y, x, g.shape));
+  J.nbr[(size_t)k * n + o] = v;
+}
+
+// ... and of the bitmap-indexed ones.  blockIdx.y: the kz plane, a thread per (row, kz plane)
+// -- 152 against 163 us at the stress size, 46 against 55 at the nominal one, with one thread
+// per row (27 dependent look-ups in a row)
+template <typename Tab>
+__global__ __launch_bounds__(256) void subm_bm_lookup_many(const Tab tab) {
+  const int s = segment_of(tab.blk0, tab.n, blockIdx.x);
+  const SubmJob& J = tab.j[s];
+  const int o = (blockIdx.x - tab.blk0[s]) * 256 + threadIdx.x;
+  if (!J.bits || o >= J.n || (int)blockIdx.y >= J.g.ks[0]) return;
+  bm_lookup_row(((const int4*)J.idx)[o], o, J.n, J.g, J.bits, J.coarse, J.block_prefix,
+                J.rank2row, J.nbr, blockIdx.y);
 }
 
 struct SubmManyWs {
@@ -821,80 +628,155 @@ int carve_subm_many(A& a, const msmd_subm_desc* d, int n_desc, SubmJob* jobs, Su
   return MSMD_OK;
 }
 
+// The argument checks of one table, and its geometry.
+int subm_check(const msmd_subm_desc& d, Geom* g) {
+  if (d.method != 0 && d.method != 1) return MSMD_ERR_INVALID_ARG;
+  const int rc = check_geom(d.spatial_shape, d.ksize, nullptr, nullptr, d.batch_size, g);
+  if (rc) return rc;
+  if (d.n < 0 || (d.n > 0 && (!d.indices || !d.nbr))) return MSMD_ERR_INVALID_ARG;
+  return MSMD_OK;
+}
+
+// *need <- the workspace of the call's largest launch set (one set at a time reuses it)
+int subm_workspace(const msmd_subm_desc* descs, int n_desc, size_t* need) {
+  *need = 0;
+  for (int g0 = 0; g0 < n_desc; g0 += kSubmMax) {
+    const int cnt = n_desc - g0 < kSubmMax ? n_desc - g0 : kSubmMax;
+    ArenaSize a;
+    const int rc = carve_subm_many(a, descs + g0, cnt, (SubmJob*)nullptr, (SubmManyWs*)nullptr);
+    if (rc) return rc;
+    *need = a.off > *need ? a.off : *need;
+  }
+  return MSMD_OK;
+}
+
+// One launch set: cnt <= N tables that passed subm_check, on a workspace that holds them.
+template <int N>
+void subm_run_set(const msmd_subm_desc* d, int cnt, void* workspace, size_t workspace_bytes,
+                  hipStream_t st) {
+  using Tab = SubmTab<N>;
+  SubmJob jobs[N] = {};
+  Arena a(workspace, workspace_bytes);
+  SubmManyWs w;
+  carve_subm_many(a, d, cnt, jobs, &w);
+  Tab tab;
+  tab.n = 0;
+  tab.blk0[0] = tab.sblk0[0] = 0;
+  int hash_y = 0, bm_y = 0;          // grid.y of the two look-ups; 0: no such table
+  bool any_flags = false;
+  for (int i = 0; i < cnt; ++i) {
+    if (d[i].n <= 0) continue;
+    SubmJob& J = jobs[i];
+    subm_check(d[i], &J.g);          // (passed before: fills the geometry)
+    J.idx = d[i].indices;
+    J.nbr = d[i].nbr;
+    J.n = d[i].n;
+    const int s = tab.n++;
+    tab.j[s] = J;
+    tab.blk0[s + 1] = tab.blk0[s] + ceil_div(J.n, 256);
+    tab.sblk0[s + 1] = tab.sblk0[s] + (J.bits ? scan_num_tiles((long)J.nblocks) : 0);
+    int& y = J.bits ? bm_y : hash_y;
+    y = std::max(y, J.bits ? J.g.ks[0] : J.g.kvol);
+    any_flags |= J.coarse != nullptr;
+  }
+  if (tab.n == 0) return;
+  for (int s = tab.n + 1; s <= N; ++s) tab.blk0[s] = tab.sblk0[s] = 0x7fffffff;
+  if (w.ones_bytes) hipMemsetAsync(w.ones, 0xFF, w.ones_bytes, st);
+  if (w.zeros_bytes) hipMemsetAsync(w.zeros, 0, w.zeros_bytes, st);
+  const int nblk = tab.blk0[tab.n];
+  MSMD_LAUNCH(subm_insert_many<Tab>, dim3(nblk), dim3(256), 0, st, tab);
+  if (bm_y) {
+    if (any_flags) MSMD_LAUNCH(subm_bm_mark_many<Tab>, dim3(nblk), dim3(256), 0, st, tab);
+    segmented_scan(tab, tab.sblk0[tab.n], w.tile_sums, st);
+    MSMD_LAUNCH(subm_bm_rows_many<Tab>, dim3(nblk), dim3(256), 0, st, tab);
+    MSMD_LAUNCH(subm_bm_lookup_many<Tab>, dim3(nblk, bm_y), dim3(256), 0, st, tab);
+  }
+  if (hash_y) MSMD_LAUNCH(subm_hash_lookup_many<Tab>, dim3(nblk, hash_y), dim3(256), 0, st, tab);
+}
+
+// One table: a launch set of one descriptor (hash index: method 0, bitmap index: method 1).
+bool subm_one_desc(msmd_subm_desc* d, const int32_t* indices, int n, int batch_size,
+                   const int* spatial_shape, const int* ksize, int method, int32_t* nbr) {
+  *d = msmd_subm_desc{};
+  if (!spatial_shape || !ksize) return false;
+  d->indices = indices;
+  d->n = n;
+  d->batch_size = batch_size;
+  for (int i = 0; i < 3; ++i) d->spatial_shape[i] = spatial_shape[i], d->ksize[i] = ksize[i];
+  d->method = method;
+  d->nbr = nbr;
+  return true;
+}
+
+int subm_one(const int32_t* indices, int n, int batch_size, const int* spatial_shape,
+             const int* ksize, int method, int32_t* nbr, void* workspace, size_t workspace_bytes,
+             msmd_stream_t stream) {
+  msmd_subm_desc d;
+  Geom g;
+  if (!subm_one_desc(&d, indices, n, batch_size, spatial_shape, ksize, method, nbr))
+    return MSMD_ERR_INVALID_ARG;
+  if (const int rc = subm_check(d, &g)) return rc;
+  if (n == 0) return MSMD_OK;       // (before any look at the workspace)
+  return msmd_rulebook_subm3d_many(&d, 1, workspace, workspace_bytes, stream);
+}
+
 }  // namespace
 
 MSMD_EXPORT size_t msmd_rulebook_subm3d_many_workspace_bytes(const msmd_subm_desc* descs,
                                                              int n_desc) {
-  if (!descs || n_desc < 0) return 0;
-  size_t most = 0;
-  for (int g0 = 0; g0 < n_desc; g0 += kSubmMax) {
-    const int cnt = n_desc - g0 < kSubmMax ? n_desc - g0 : kSubmMax;
-    ArenaSize a;
-    if (carve_subm_many(a, descs + g0, cnt, (SubmJob*)nullptr, (SubmManyWs*)nullptr) != MSMD_OK)
-      return 0;
-    most = a.off > most ? a.off : most;
-  }
-  return most;
+  size_t need;
+  if (!descs || n_desc < 0 || subm_workspace(descs, n_desc, &need) != MSMD_OK) return 0;
+  return need;
 }
 
+// Every descriptor, then the workspace against the largest launch set, are checked before the
+// first fill or launch: a refused call leaves every table untouched.
 MSMD_EXPORT int msmd_rulebook_subm3d_many(const msmd_subm_desc* descs, int n_desc, void* workspace,
                                           size_t workspace_bytes, msmd_stream_t stream) {
   if (n_desc < 0 || (n_desc > 0 && !descs)) return MSMD_ERR_INVALID_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  for (int g0 = 0; g0 < n_desc; g0 += kSubmMax) {
-    const int cnt = n_desc - g0 < kSubmMax ? n_desc - g0 : kSubmMax;
-    const msmd_subm_desc* d = descs + g0;
-    SubmTab tab;
-    SubmJob jobs[kSubmMax];
-    for (int i = 0; i < cnt; ++i) {
-      jobs[i] = SubmJob{};
-      if (d[i].method != 0 && d[i].method != 1) return MSMD_ERR_INVALID_ARG;
-      const int rc = check_geom(d[i].spatial_shape, d[i].ksize, nullptr, nullptr, d[i].batch_size,
-                                &jobs[i].g);
-      if (rc) return rc;
-      if (d[i].n < 0 || (d[i].n > 0 && (!d[i].indices || !d[i].nbr))) return MSMD_ERR_INVALID_ARG;
-      jobs[i].idx = d[i].indices;
-      jobs[i].nbr = d[i].nbr;
-      jobs[i].n = d[i].n;
-    }
-    Arena a(workspace, workspace_bytes);
-    SubmManyWs w;
-    const int rc = carve_subm_many(a, d, cnt, jobs, &w);
-    if (rc) return rc;
-    if (!a.ok()) return MSMD_ERR_WORKSPACE;
-    tab.n = 0;
-    tab.blk0[0] = tab.sblk0[0] = 0;
-    int max_y = 1;
-    bool any_bitmap = false, any_flags = false;
-    for (int i = 0; i < cnt; ++i) {
-      if (jobs[i].n <= 0) continue;
-      const int s = tab.n++;
-      tab.j[s] = jobs[i];
-      tab.blk0[s + 1] = tab.blk0[s] + ceil_div(jobs[i].n, 256);
-      tab.sblk0[s + 1] = tab.sblk0[s] + (jobs[i].bits ? scan_num_tiles((long)jobs[i].nblocks) : 0);
-      const Geom& g = jobs[i].g;
-      const int y = jobs[i].bits ? g.ks[0] : g.kvol;
-      max_y = y > max_y ? y : max_y;
-      any_bitmap |= jobs[i].bits != nullptr;
-      any_flags |= jobs[i].coarse != nullptr;
-    }
-    if (tab.n == 0) continue;
-    for (int s = tab.n + 1; s <= kSubmMax; ++s) tab.blk0[s] = tab.sblk0[s] = 0x7fffffff;
-    if (w.ones_bytes) hipMemsetAsync(w.ones, 0xFF, w.ones_bytes, st);
-    if (w.zeros_bytes) hipMemsetAsync(w.zeros, 0, w.zeros_bytes, st);
-    const int nblk = tab.blk0[tab.n];
-    MSMD_LAUNCH(subm_insert_many, dim3(nblk), dim3(256), 0, st, tab);
-    if (any_bitmap) {
-      if (any_flags) MSMD_LAUNCH(subm_bm_mark_many, dim3(nblk), dim3(256), 0, st, tab);
-      const int nt = tab.sblk0[tab.n];
-      MSMD_LAUNCH(subm_bm_sums_many, dim3(nt), dim3(kScanBlock), 0, st, tab, w.tile_sums);
-      MSMD_LAUNCH(subm_bm_prefix_many, dim3(nt), dim3(kScanBlock), 0, st, tab,
-                  (const int*)w.tile_sums);
-      MSMD_LAUNCH(subm_bm_rows_many, dim3(nblk), dim3(256), 0, st, tab);
-    }
-    MSMD_LAUNCH(subm_lookup_many, dim3(nblk, max_y), dim3(256), 0, st, tab);
-  }
+  Geom g;
+  for (int i = 0; i < n_desc; ++i)
+    if (const int rc = subm_check(descs[i], &g)) return rc;
+  size_t need;
+  if (const int rc = subm_workspace(descs, n_desc, &need)) return rc;   // (2^24 bricks: RANGE)
+  if (workspace_bytes < need || ((uintptr_t)workspace & 255)) return MSMD_ERR_WORKSPACE;
+  if (n_desc == 1) subm_run_set<1>(descs, 1, workspace, workspace_bytes, (hipStream_t)stream);
+  for (int g0 = 0; n_desc > 1 && g0 < n_desc; g0 += kSubmMax)
+    subm_run_set<kSubmMax>(descs + g0, n_desc - g0 < kSubmMax ? n_desc - g0 : kSubmMax, workspace,
+                           workspace_bytes, (hipStream_t)stream);
   return launch_status();
+}
+
+MSMD_EXPORT size_t msmd_rulebook_subm_workspace_bytes(int n) {
+  msmd_subm_desc d = {};
+  d.n = n;
+  return msmd_rulebook_subm3d_many_workspace_bytes(&d, 1);
+}
+
+MSMD_EXPORT int msmd_rulebook_subm3d(const int32_t* indices, int n, int batch_size,
+                                     const int* spatial_shape, const int* ksize, int32_t* nbr,
+                                     void* workspace, size_t workspace_bytes,
+                                     msmd_stream_t stream) {
+  return subm_one(indices, n, batch_size, spatial_shape, ksize, 0, nbr, workspace,
+                  workspace_bytes, stream);
+}
+
+MSMD_EXPORT size_t msmd_rulebook_subm_bitmap_workspace_bytes(int n, int batch_size,
+                                                             const int* spatial_shape) {
+  const int ks[3] = {1, 1, 1};
+  msmd_subm_desc d;
+  if (n < 0 || batch_size < 1 ||
+      !subm_one_desc(&d, nullptr, n, batch_size, spatial_shape, ks, 1, nullptr))
+    return 0;
+  return msmd_rulebook_subm3d_many_workspace_bytes(&d, 1);
+}
+
+MSMD_EXPORT int msmd_rulebook_subm3d_bitmap(const int32_t* indices, int n, int batch_size,
+                                            const int* spatial_shape, const int* ksize,
+                                            int32_t* nbr, void* workspace,
+                                            size_t workspace_bytes, msmd_stream_t stream) {
+  return subm_one(indices, n, batch_size, spatial_shape, ksize, 1, nbr, workspace,
+                  workspace_bytes, stream);
 }
 
 // --------------------------------------------------- strided / transposed ---

@@ -9,6 +9,8 @@
 // Used for: popcount ranks of occupancy bitmaps (strided rulebook,
 // sparse_add, modality split), first-point flags (voxelization) and per-offset
 // pair compaction.  All HBM-bound streaming passes with coalesced access.
+// segmented_scan() below runs the same two kernels over several independent sequences at
+// once (the launch sets of voxelize.hip, rulebook.hip and dense.hip).
 #pragma once
 #include "common.hpp"
 
@@ -23,11 +25,12 @@ inline int scan_num_tiles(long n) { return ceil_div(n, kScanTile); }
 // run of whole tiles, so no tile straddles two offsets).
 inline int rows_padded(int n_rows) { return scan_num_tiles(n_rows > 0 ? n_rows : 1) * kScanTile; }
 
+// Sum of the tile's counts -> *out.  The tile covers elements [base, base + kScanTile) of
+// a sequence of n.
 template <typename Count>
-__global__ __launch_bounds__(kScanBlock) void scan_tile_sums(Count count, int n,
-                                                             int* __restrict__ tile_sums) {
+__device__ __forceinline__ void tile_sum(const Count& count, int base, int n,
+                                         int* __restrict__ out) {
   __shared__ int smem[kScanBlock / 64];
-  const int base = blockIdx.x * kScanTile;
   int s = 0;
 #pragma unroll
   for (int j = 0; j < kScanItems; ++j) {
@@ -40,8 +43,14 @@ __global__ __launch_bounds__(kScanBlock) void scan_tile_sums(Count count, int n,
   if (threadIdx.x == 0) {
     int t = 0;
     for (int i = 0; i < kScanBlock / 64; ++i) t += smem[i];
-    tile_sums[blockIdx.x] = t;
+    *out = t;
   }
+}
+
+template <typename Count>
+__global__ __launch_bounds__(kScanBlock) void scan_tile_sums(Count count, int n,
+                                                             int* __restrict__ tile_sums) {
+  tile_sum(count, blockIdx.x * kScanTile, n, tile_sums + blockIdx.x);
 }
 
 // Sum of a[lo .. hi) by the whole block (same value in every thread).  smem: BLOCK/64 ints.
@@ -128,28 +137,81 @@ static __global__ void scan_empty_total(int* __restrict__ total) {
   if (total) *total = 0;
 }
 
+// The tile at [base, base + kScanTile) of a sequence of n: emit(i, exclusive prefix, value) for
+// its elements, the prefix starting from the sum of tile_sums[lo .. hi), the tiles of the
+// sequence in front of this one.  Returns the inclusive total at the tile's end.
 template <typename Count, typename Emit>
-__global__ __launch_bounds__(kScanBlock) void scan_apply(Count count, Emit emit, int n,
-                                                         const int* __restrict__ tile_sums,
-                                                         int* __restrict__ total, int clamp) {
+__device__ __forceinline__ int tile_apply(const Count& count, const Emit& emit, int base, int n,
+                                          const int* __restrict__ tile_sums, int lo, int hi) {
   __shared__ int smem[kScanSmem];
-  const int base = blockIdx.x * kScanTile;
   int v[kScanItems], ex[kScanItems];
 #pragma unroll
   for (int j = 0; j < kScanItems; ++j) {
     const int i = base + j * kScanBlock + threadIdx.x;
     v[j] = i < n ? count(i) : 0;
   }
-  int carry = block_range_sum<kScanBlock>(tile_sums, 0, blockIdx.x, smem);
+  const int carry = block_range_sum<kScanBlock>(tile_sums, lo, hi, smem);
   const int tot = tile_excl_scan(v, ex, smem);
 #pragma unroll
   for (int j = 0; j < kScanItems; ++j) {
     const int i = base + j * kScanBlock + threadIdx.x;
     if (i < n) emit(i, carry + ex[j], v[j]);
   }
-  carry += tot;
+  return carry + tot;
+}
+
+template <typename Count, typename Emit>
+__global__ __launch_bounds__(kScanBlock) void scan_apply(Count count, Emit emit, int n,
+                                                         const int* __restrict__ tile_sums,
+                                                         int* __restrict__ total, int clamp) {
+  const int sum = tile_apply(count, emit, blockIdx.x * kScanTile, n, tile_sums, 0, blockIdx.x);
   if (total && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0)
-    *total = (clamp >= 0 && carry > clamp) ? clamp : carry;
+    *total = (clamp >= 0 && sum > clamp) ? clamp : sum;
+}
+
+// ---- several sequences in one launch ----------------------------------------
+// The launch sets (msmd_hard_voxelize_many, msmd_rulebook_subm3d_many, msmd_rows_where_eq_many,
+// msmd_rulebook_plan_many) pack the blocks of several jobs into one grid; `first` holds each
+// job's first block (n + 1 entries, the unused tail at INT_MAX) and travels as a kernel
+// argument.  -> the job that owns block b.  A table with room for one job needs no look-up:
+// its blocks read the job's fields at fixed offsets, without waiting for `first`.
+template <int M>
+__device__ __forceinline__ int segment_of(const int (&first)[M], int n, int b) {
+  if (M == 2) return 0;
+  int s = 0;
+  while (s + 1 < n && b >= first[s + 1]) ++s;     // uniform: scalar loads of kernel arguments
+  return s;
+}
+
+// The scan above over several independent segments, each owning whole tiles (the scan restarts
+// at every segment).  Tab, a launch table passed by value, supplies
+//   int n;                                   -- number of segments
+//   const int (&seg_tile0() const)[]         -- first tile of segment s (n + 1 entries)
+//   int seg_len(int s) const                 -- its number of elements
+//   Count seg_count(int s), Emit seg_emit(int s) const   -- the contracts at the top
+//   void seg_done(int s, int total) const    -- run by every thread of the block that holds the
+//                                               segment's last tile, with the segment's sum
+template <typename Tab>
+__global__ __launch_bounds__(kScanBlock) void seg_scan_tile_sums(const Tab tab,
+                                                                 int* __restrict__ tile_sums) {
+  const int s = segment_of(tab.seg_tile0(), tab.n, blockIdx.x);
+  tile_sum(tab.seg_count(s), (blockIdx.x - tab.seg_tile0()[s]) * kScanTile, tab.seg_len(s),
+           tile_sums + blockIdx.x);
+}
+template <typename Tab>
+__global__ __launch_bounds__(kScanBlock) void seg_scan_apply(const Tab tab,
+                                                             const int* __restrict__ tile_sums) {
+  const int s = segment_of(tab.seg_tile0(), tab.n, blockIdx.x);
+  const int t0 = tab.seg_tile0()[s];
+  const int sum = tile_apply(tab.seg_count(s), tab.seg_emit(s), (blockIdx.x - t0) * kScanTile,
+                             tab.seg_len(s), tile_sums, t0, (int)blockIdx.x);
+  if ((int)blockIdx.x == tab.seg_tile0()[s + 1] - 1) tab.seg_done(s, sum);
+}
+template <typename Tab>
+inline void segmented_scan(const Tab& tab, int n_tiles, int* tile_sums, hipStream_t st) {
+  MSMD_LAUNCH(seg_scan_tile_sums<Tab>, dim3(n_tiles), dim3(kScanBlock), 0, st, tab, tile_sums);
+  MSMD_LAUNCH(seg_scan_apply<Tab>, dim3(n_tiles), dim3(kScanBlock), 0, st, tab,
+              (const int*)tile_sums);
 }
 
 // Host driver.  tile_sums: scratch of scan_num_tiles(n) ints (raw tile sums afterwards).

@@ -158,6 +158,88 @@ def test_planning_calls_refuse_bad_arguments_host_side():
     assert many(desc(kvol=31, n_rows=1 << 27, ld=1 << 27), 1, p, big, None) == RANGE
 
 
+def test_many_calls_refuse_a_bad_descriptor_of_a_later_launch_set_host_side():
+    """msmd_hard_voxelize_many, msmd_rulebook_subm3d_many and msmd_rows_where_eq_many check
+    every descriptor of the call, and the first two the workspace against the largest launch
+    set, before the first fill or launch: a bad entry in a LATER launch set (12, 16 and 16
+    entries per set) is refused with nothing enqueued -- here, where there is no device to
+    enqueue on.  The single calls are the one-descriptor case and return their codes as before
+    (test_host_side_argument_validation)."""
+    from msmdfusion_amd import kernels as K
+    from msmdfusion_amd._lib import float_arr, int3, lib
+    INVALID, WORKSPACE, RANGE = -1, -2, -5
+    p, big = ctypes.c_void_p(256), 1 << 30        # (never dereferenced: every call is refused)
+
+    vox = (K._VoxDesc * 13)()
+    for d in vox:
+        d.points, d.num_points, d.num_features = 256, 100, 5
+        d.voxel_size[:] = [0.1] * 3
+        d.coors_range[:] = [0, 0, 0, 1, 1, 1]
+        d.max_points, d.max_voxels = 10, 50
+        d.coors = d.num_points_per_voxel = d.voxel_num = 256
+    many = lib.msmd_hard_voxelize_many
+    assert lib.msmd_hard_voxelize_many_workspace_bytes(vox, 13) > 0
+    assert many(vox, 13, p, 0, None) == WORKSPACE
+    assert many(vox, 13, ctypes.c_void_p(260), big, None) == WORKSPACE
+    vox[12].max_points = 0
+    assert many(vox, 13, p, big, None) == INVALID
+    vox[12].max_points = 10
+    vox[12].voxel_size[:] = [1e-4] * 3                    # 10^12 cells
+    assert many(vox, 13, p, big, None) == RANGE
+    vox[12].voxel_size[:] = [10.0] * 3                    # a grid of 0 cells
+    assert many(vox, 13, p, big, None) == INVALID
+    assert many(None, 1, p, big, None) == INVALID and many(vox, 0, p, big, None) == INVALID
+    one = lib.msmd_hard_voxelize
+    args = (float_arr([0.1] * 3), float_arr([0, 0, 0, 1, 1, 1]), 10, 50, None, p, p, None, p)
+    assert one(p, 100, 5, *args, p, 0, None) == WORKSPACE
+    assert one(p, 100, 5, *args, p, lib.msmd_voxelize_workspace_bytes(100, 50, 10) - 1,
+               None) == WORKSPACE
+    assert one(p, 100, 2, *args, p, big, None) == INVALID
+    assert one(p, 100, 5, float_arr([1e-4] * 3), *args[1:], p, big, None) == RANGE
+
+    subm = (K._SubmDesc * 17)()
+    for d in subm:
+        d.indices, d.n, d.batch_size, d.nbr = 256, 100, 1, 256
+        d.spatial_shape[:] = [8, 64, 64]
+        d.ksize[:] = [3, 3, 3]
+        d.method = 1
+    many = lib.msmd_rulebook_subm3d_many
+    assert lib.msmd_rulebook_subm3d_many_workspace_bytes(subm, 17) > 0
+    assert many(subm, 17, p, 0, None) == WORKSPACE
+    subm[16].method = 2
+    assert many(subm, 17, p, big, None) == INVALID
+    subm[16].method = 1
+    subm[16].spatial_shape[:] = [1, 32768, 32768]        # 2^24 bricks: no bitmap index
+    assert many(subm, 17, p, big, None) == RANGE
+    subm[16].spatial_shape[:] = [70000] * 3
+    assert many(subm, 17, p, big, None) == RANGE
+    subm[16].spatial_shape[:] = [8, 64, 64]
+    subm[16].n = -1
+    assert many(subm, 17, p, big, None) == INVALID
+    assert many(None, 0, None, 0, None) == 0
+    shape, ks = int3([8, 64, 64]), int3([3, 3, 3])
+    for one, need in ((lib.msmd_rulebook_subm3d, lib.msmd_rulebook_subm_workspace_bytes(100)),
+                      (lib.msmd_rulebook_subm3d_bitmap,
+                       lib.msmd_rulebook_subm_bitmap_workspace_bytes(100, 1, shape))):
+        assert need > 0
+        assert one(p, 100, 1, shape, ks, p, p, need - 1, None) == WORKSPACE
+        assert one(p, 100, 1, shape, ks, p, ctypes.c_void_p(260), big, None) == WORKSPACE
+        assert one(None, 0, 1, shape, ks, None, None, 0, None) == 0      # empty: before the workspace
+        assert one(p, 100, 1, shape, ks, None, p, big, None) == INVALID
+    assert lib.msmd_rulebook_subm3d_bitmap(p, 100, 1, int3([1, 32768, 32768]), ks, p, p, big,
+                                           None) == RANGE
+
+    n = 17
+    flags, rows = (ctypes.c_void_p * n)(*[256] * n), (ctypes.c_void_p * n)(*[256] * n)
+    ints = lambda v: (ctypes.c_int * n)(*[v] * n)          # noqa: E731
+    strides, lens, values, caps = ints(1), ints(100), ints(1), ints(10)
+    many = lib.msmd_rows_where_eq_many
+    strides[16] = 0
+    assert many(flags, strides, lens, values, rows, caps, n, p, big, None) == INVALID
+    strides[16] = 1
+    assert many(flags, strides, lens, values, rows, caps, n, p, 0, None) == WORKSPACE
+
+
 def test_product_never_touches_the_oracle():
     """oracle/ is test infrastructure: nothing under msmdfusion_amd/ may import
     or call it, and the package has no CPU fallback branches."""

@@ -71,6 +71,36 @@ def test_hard_voxelize_edge_cases(dev):
     ev, ec, en = O.hard_voxelize(edge, S.VOXEL_SIZE, S.POINT_CLOUD_RANGE, 10, 1000)
     v, c, n, _ = K.hard_voxelize(t(edge, dev), S.VOXEL_SIZE, S.POINT_CLOUD_RANGE, 10, 1000)
     assert np.array_equal(c.cpu().numpy(), ec) and np.array_equal(n.cpu().numpy(), en)
+    # the edges of the 2048-point scan tile: one point, a full tile, one and two tiles and a
+    # point; the max_voxels break in the first tile, in the second tile and nowhere
+    rg = S.POINT_CLOUD_RANGE
+    for n_pts in (1, 2048, 2049, 4097):
+        p = rng.randn(n_pts, 5).astype(np.float32)
+        p[:, 0] = rng.uniform(rg[0] * 0.004, rg[3] * 0.004, n_pts)   # ~1500 cells: shared voxels
+        p[:, 1] = rng.uniform(rg[1] * 0.004, rg[4] * 0.004, n_pts)
+        p[:, 2] = rng.uniform(rg[2], rg[5], n_pts)
+        p[-1, :3] = (40.0, 40.0, 0.0)                  # the last point opens a voxel of its own
+        first = O.hard_voxelize(p[:2048], S.VOXEL_SIZE, rg, 10, 10000)[1].shape[0]
+        for max_points in (1, 10):
+            # `first`: the voxels of the first tile fill the cap, so with more than 2048 points
+            # the break falls on the first point of the second tile that opens a voxel
+            for max_voxels in (10000, 3, first):
+                ev, ec, en = O.hard_voxelize(p, S.VOXEL_SIZE, rg, max_points, max_voxels)
+                v, c, n, mean = K.hard_voxelize(t(p, dev), S.VOXEL_SIZE, rg, max_points, max_voxels,
+                                                want_voxels=True, want_mean=True)
+                what = (n_pts, max_points, max_voxels)
+                assert np.array_equal(c.cpu().numpy(), ec), what
+                assert np.array_equal(n.cpu().numpy(), en), what
+                assert np.array_equal(v.cpu().numpy(), ev), what
+                np.testing.assert_allclose(mean.cpu().numpy(), O.voxel_mean(ev, en), rtol=1e-6,
+                                           atol=1e-6)
+        if n_pts > 2048:
+            assert O.hard_voxelize(p, S.VOXEL_SIZE, rg, 10, 10000)[1].shape[0] > first > 3
+    # a non-empty scan that finds nothing: two tiles of points out of range
+    far = (rng.rand(2049, 5) + 100).astype(np.float32)
+    v, c, n, _ = K.hard_voxelize(t(far, dev), S.VOXEL_SIZE, rg, 10, 1000)
+    assert O.hard_voxelize(far, S.VOXEL_SIZE, rg, 10, 1000)[1].shape[0] == 0
+    assert c.shape[0] == 0 and v.shape[0] == 0 and n.shape[0] == 0
 
 
 # ------------------------------------------------------------------ rulebooks
@@ -290,21 +320,18 @@ def test_rulebook_plan_equals_its_parts(dev, n_vox):
     assert torch.equal(again["prefix"][128], plan["prefix"][128])
 
 
-def test_rulebook_subm_many_equals_the_single_calls(dev):
+def test_rulebook_subm_many_and_single_calls_against_the_numpy_table(dev):
     """msmd_rulebook_subm3d_many -- the SubM tables of several voxel sets from one launch set,
     hash-indexed and bitmap-indexed sets mixed, different grids, kernel sizes and batch
-    sizes -- equals msmd_rulebook_subm3d / _bitmap set by set (duplicate coordinates keep the
-    last row in both); 19 sets = two launch sets."""
+    sizes -- and msmd_rulebook_subm3d / _bitmap (its one-descriptor case) set by set, against
+    the dense numpy table of tests/subm_table_ref.py (duplicate coordinates: every row finds
+    the last row of the coordinate); 19 sets = two launch sets."""
+    import subm_table_ref as R
     from msmdfusion_amd import kernels as K
-    cases = [(5000, 2, [11, 64, 64], 3, "hash"), (5000, 2, [11, 64, 64], 3, "bitmap"),
-             (1, 1, [5, 8, 8], 3, "bitmap"), (130, 3, [7, 30, 30], [3, 3, 1], "hash"),
-             (2600, 2, [11, 64, 64], [1, 3, 3], "bitmap"), (9000, 4, [21, 90, 90], 3, None),
-             (700, 1, [41, 200, 200], 3, None), (3000, 2, [3, 100, 100], [3, 5, 3], "bitmap")]
-    jobs = []
-    for seed, (n_vox, batch, shape, ks, method) in enumerate(cases):
-        idx = S.random_voxel_indices(n_vox, batch, shape, seed=seed)
-        if seed == 0:                       # duplicate coordinates: the last row wins
-            idx = np.concatenate([idx, idx[:37]])
+    jobs, want = [], []
+    for i, (n_vox, batch, shape, ks, method) in enumerate(R.CASES):
+        idx = R.case_indices(i)
+        want.append(R.subm_table(idx, batch, shape, ks))
         ti = t(idx, dev)
         jobs.append(dict(indices=ti, batch_size=batch, spatial_shape=shape, ksize=ks,
                          method=method, nbr=K.subm_table(ti, ks)))
@@ -312,19 +339,91 @@ def test_rulebook_subm_many_equals_the_single_calls(dev):
         for j in jobs:
             j["nbr"].fill_(-7)
         K.rulebook_subm_many(jobs)
-        for j in jobs:
-            ref = K.rulebook_subm(j["indices"], j["batch_size"], j["spatial_shape"], j["ksize"],
+        for j, exp in zip(jobs, want):
+            what = (j["indices"].shape, j["ksize"], j["method"])
+            assert np.array_equal(j["nbr"].cpu().numpy(), exp), what
+            one = K.rulebook_subm(j["indices"], j["batch_size"], j["spatial_shape"], j["ksize"],
                                   method=j["method"])
-            assert torch.equal(j["nbr"], ref), (j["indices"].shape, j["ksize"], j["method"])
+            assert np.array_equal(one.cpu().numpy(), exp), what
     many = [dict(jobs[i % 5], nbr=K.subm_table(jobs[i % 5]["indices"], jobs[i % 5]["ksize"]))
             for i in range(19)]
     K.rulebook_subm_many(many)
     for i, j in enumerate(many):
-        assert torch.equal(j["nbr"], jobs[i % 5]["nbr"])
+        assert np.array_equal(j["nbr"].cpu().numpy(), want[i % 5]), i
     K.rulebook_subm_many([])
     empty = t(np.zeros((0, 4), np.int32), dev)
     K.rulebook_subm_many([dict(indices=empty, batch_size=1, spatial_shape=[4, 4, 4], ksize=3,
                                nbr=K.subm_table(empty, 3))])
+
+
+@pytest.mark.parametrize("shape,n_vox", [([4, 256, 512], 300), ([4, 264, 512], 300),
+                                         ([4, 256, 512], 40000), ([4, 256, 512], 1),
+                                         ([4, 264, 512], 2049)])
+def test_rulebook_subm_at_the_scan_tile_edges(dev, shape, n_vox):
+    """The bitmap index scans 256-cell bricks in tiles of 2048: a grid of exactly 2048 bricks
+    and one of 2112 (two tiles); a few hundred voxels (one flag byte per brick says which
+    bricks to count) and 40000 (the whole bitmap is cleared instead); 1 row and 2049 rows for
+    the passes with a thread per row.  Both index methods against the numpy table."""
+    import subm_table_ref as R
+    from msmdfusion_amd import kernels as K
+    bricks = ((shape[0] + 3) // 4) * ((shape[1] + 7) // 8) * ((shape[2] + 7) // 8)
+    assert bricks == (2048 if shape[1] == 256 else 2112)
+    idx = S.random_voxel_indices(n_vox, 1, shape, seed=n_vox, clustered=False)
+    assert idx.shape[0] == n_vox
+    # csrc/rulebook.hip bm_use_flags: flag bytes when the bitmap has > 64 bytes per voxel
+    assert (bricks * 32 > 64 * n_vox) == (n_vox <= 300)
+    exp = R.subm_table(idx, 1, shape, 3)
+    for method in ("bitmap", "hash"):
+        got = K.rulebook_subm(t(idx, dev), 1, shape, 3, method=method)
+        assert np.array_equal(got.cpu().numpy(), exp), method
+    nbr = K.subm_table(t(idx, dev), 3)
+    K.rulebook_subm_many([dict(indices=t(idx, dev), batch_size=1, spatial_shape=shape, ksize=3,
+                               method="bitmap", nbr=nbr)])
+    assert np.array_equal(nbr.cpu().numpy(), exp)
+
+
+def test_many_calls_validate_every_descriptor_before_the_first_launch(dev):
+    """A bad descriptor in a LATER launch set (the 13th cloud of 12 per set, the 17th SubM job
+    of 16 per set) is refused with MSMD_ERR_INVALID_ARG before anything of the earlier sets is
+    enqueued: every output keeps the value it held."""
+    from msmdfusion_amd import kernels as K
+    from msmdfusion_amd._lib import lib
+    rng = np.random.RandomState(3)
+    rg = S.POINT_CLOUD_RANGE
+    pts = t((rng.rand(200, 5) * 4 - 2).astype(np.float32), dev)
+    counts = torch.full((13,), -7, dtype=torch.int32, device=dev)
+    coors = torch.empty((50, 3), dtype=torch.int32, device=dev)
+    npv = torch.empty((50,), dtype=torch.int32, device=dev)
+    descs = (K._VoxDesc * 13)()
+    for i, d in enumerate(descs):
+        d.points, d.num_points, d.num_features = pts.data_ptr(), 200, 5
+        d.voxel_size[:] = S.VOXEL_SIZE
+        d.coors_range[:] = rg
+        d.max_points, d.max_voxels = 10, 50
+        d.coors, d.num_points_per_voxel = coors.data_ptr(), npv.data_ptr()
+        d.voxel_num = counts[i:i + 1].data_ptr()
+    nbytes = lib.msmd_hard_voxelize_many_workspace_bytes(descs, 13)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    descs[12].max_points = 0
+    assert lib.msmd_hard_voxelize_many(descs, 13, ws.data_ptr(), nbytes, None) == -1
+    torch.cuda.synchronize()
+    assert (counts == -7).all()
+
+    idx = t(S.random_voxel_indices(300, 1, [5, 16, 16], seed=1), dev)
+    tables = [K.subm_table(idx, 3).fill_(-7) for _ in range(17)]
+    jobs = (K._SubmDesc * 17)()
+    for d, nbr in zip(jobs, tables):
+        d.indices, d.n, d.batch_size = idx.data_ptr(), idx.shape[0], 1
+        d.spatial_shape[:] = [5, 16, 16]
+        d.ksize[:] = [3, 3, 3]
+        d.method, d.nbr = 0, nbr.data_ptr()
+    nbytes = lib.msmd_rulebook_subm3d_many_workspace_bytes(jobs, 17)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    jobs[16].method = 2
+    assert lib.msmd_rulebook_subm3d_many(jobs, 17, ws.data_ptr(), nbytes, None) == -1
+    torch.cuda.synchronize()
+    for nbr in tables:
+        assert (nbr == -7).all()
 
 
 def test_add_conv_chain_equals_stage_by_stage(dev):
@@ -1363,13 +1462,12 @@ def test_pack_weight_split_pair(dev, cin, cout, krsc):
         assert torch.equal(b, K.pack_weight_split(w, planes, transpose=True, krsc=krsc))
 
 
-def test_hard_voxelize_many_equals_cloud_by_cloud(dev, monkeypatch):
+def test_hard_voxelize_many_against_the_oracle(dev):
     """msmd_hard_voxelize_many (every cloud of a batch in one launch set: blocks find their
-    cloud, the scan restarts per cloud, one fill for all tables) == msmd_hard_voxelize called
-    cloud by cloud, bit for bit: mixed channel counts and voxel sizes (the LiDAR sweeps + the
-    four virtual-point scales of an LC step), a cloud below one scan tile, an EMPTY cloud, a
-    cloud that hits max_voxels (the reference loop's `break`), 14 clouds = two launch sets;
-    and against the oracle for one of them."""
+    cloud, the scan restarts per cloud, one fill for all tables) against the CPU oracle, cloud
+    by cloud: mixed channel counts and voxel sizes (the LiDAR sweeps + the four virtual-point
+    scales of an LC step), a cloud below one scan tile, an EMPTY cloud, a cloud that hits
+    max_voxels (the reference loop's `break`), 14 clouds = two launch sets."""
     from msmdfusion_amd import kernels as K
     rng = np.random.RandomState(12)
     rg = S.POINT_CLOUD_RANGE
@@ -1391,22 +1489,23 @@ def test_hard_voxelize_many_equals_cloud_by_cloud(dev, monkeypatch):
     sizes = sizes + sizes
     d = [t(c, dev) for c in clouds]
     for max_voxels in (20000, 700):        # 700: several clouds run into the cap
+        want = [O.hard_voxelize(c, s, rg, 10, max_voxels) for c, s in zip(clouds, sizes)]
+        assert want[5][0].shape == (0, 10, 5) and want[5][1].shape == (0, 3)
+        assert want[5][2].shape == (0,)
         for want_voxels, want_mean in ((True, False), (False, True), (True, True)):
-            monkeypatch.setattr(K, "VOXELIZE_MANY", True)
             got = K.hard_voxelize_batch(d, sizes, rg, 10, max_voxels, want_voxels, want_mean)
-            monkeypatch.setattr(K, "VOXELIZE_MANY", False)
-            ref = K.hard_voxelize_batch(d, sizes, rg, 10, max_voxels, want_voxels, want_mean)
-            assert len(got) == len(ref) == len(clouds)
-            for ci, (a, b) in enumerate(zip(got, ref)):
-                for x, y in zip(a, b):
-                    assert (x is None) == (y is None), ci
-                    if x is not None:
-                        assert x.shape == y.shape and torch.equal(x, y), (ci, max_voxels)
+            assert len(got) == len(clouds)
+            for ci, ((v, c, n, mean), (ev, ec, en)) in enumerate(zip(got, want)):
+                what = (ci, max_voxels)
+                assert (v is not None) == want_voxels and (mean is not None) == want_mean, what
+                assert np.array_equal(c.cpu().numpy(), ec), what
+                assert np.array_equal(n.cpu().numpy(), en), what
+                if want_voxels:
+                    assert np.array_equal(v.cpu().numpy(), ev), what   # copies: bit exact
+                if want_mean:
+                    np.testing.assert_allclose(mean.cpu().numpy(), O.voxel_mean(ev, en),
+                                               rtol=1e-6, atol=1e-6)
             assert got[5][1].shape[0] == 0                       # the empty cloud
         if max_voxels == 700:
+            assert want[0][1].shape[0] == 700
             assert sum(int(g[1].shape[0] == 700) for g in got) >= 4
-    monkeypatch.setattr(K, "VOXELIZE_MANY", True)
-    got = K.hard_voxelize_batch(d, sizes, rg, 10, 20000, True, False)
-    ev, ec, en = O.hard_voxelize(clouds[2], sizes[2], rg, 10, 20000)
-    assert np.array_equal(got[2][1].cpu().numpy(), ec) and np.array_equal(got[2][2].cpu().numpy(), en)
-    assert np.array_equal(got[2][0].cpu().numpy(), ev)

@@ -325,3 +325,27 @@ def test_sparse_add_equals_torch_coo_add_and_coalesce():
     np.testing.assert_allclose(tc.values().numpy(), of, rtol=1e-6, atol=1e-6)
     # the row maps point every operand row at its coordinate's output row
     assert np.array_equal(oi[ma], a) and np.array_equal(oi[mb], b)
+
+
+def test_subm_numpy_table_equals_the_oracle():
+    """tests/subm_table_ref.py, the dense-grid table the SubM rulebook tests compare the
+    kernels with, equals get_indice_pairs on the duplicate-free cases; where coordinates
+    repeat (the oracle leaves the columns of shadowed rows at -1, the kernels pair every row
+    with the last row of its coordinate) the centre entry of both the shadowed rows and their
+    winners is the winner."""
+    import subm_table_ref as R
+    for i, (_, batch, shape, ks, _) in enumerate(R.CASES):
+        idx = R.case_indices(i)
+        exp = R.subm_table(idx, batch, shape, ks)
+        if i == 0:
+            n, dup = idx.shape[0], R.N_DUPLICATES
+            assert n == R.CASES[0][0] + dup
+            winners = np.arange(n - dup, n)
+            assert np.array_equal(exp[13, :dup], winners) and np.array_equal(exp[13, n - dup:], winners)
+            continue
+        _, pr, nm, _ = O.get_indice_pairs(idx, batch, shape, ks, 1, 0, 1, True)
+        want = np.full_like(exp, -1)
+        for k in range(nm.shape[0]):
+            p = int(nm[k])
+            want[k, pr[k, 1, :p]] = pr[k, 0, :p]
+        assert np.array_equal(exp, want), (i, ks)
