@@ -456,6 +456,14 @@ int msmd_spconv_fwd_f32(const float* in_feat /* [n_in,c_in] */, int n_in,
  * cycles than the fp32 MFMA.  `planes` = 3 is that mode; 2 keeps three products
  * (relative error ~2^-17); 1 is plain bf16 operands.  Features are read as fp32
  * and split in registers; weights are split by the pack call.
+ * Non-finite operands: a NaN stays NaN.  An INFINITE operand becomes NaN with planes >= 2,
+ * where msmd_spconv_fwd_f32 returns inf: the first plane is bf16(inf) = inf and the
+ * residual plane inf - inf = NaN.  planes = 1 has no residual and returns inf like the fp32
+ * kernel.  Either way exactly the output rows connected to the operand's row change (every
+ * element of them: a zero weight does not mask a NaN); all other rows are bit-identical to
+ * the clean run under every scheduling mode, and a row that no table entry refers to is
+ * never read.  The same holds for msmd_spconv_wgrad_split per kernel offset
+ * (tests/test_gpu_conv_edges.py pins both).
  * Covers c_in % 8 == 0 and c_out % 4 == 0, both >= 32, K <= 32 (ask
  * msmd_spconv_fwd_split_supported; c_out > 128 runs in column passes); other
  * layers use msmd_spconv_fwd_f32.
