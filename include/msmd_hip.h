@@ -1971,6 +1971,90 @@ int msmd_primitive_targets_f32(const float* points /* [total_points,ld] */, int 
                                float* point_sem /* [total_points,3+num_dims+1] */,
                                msmd_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * n8  H3DNet second stage: box cue centres and fused cue targets (csrc/h3d.hip)
+ * replaces: DepthInstance3DBoxes.get_surface_line_center
+ *           mmdet3d/core/bbox/structures/depth_box3d.py:277-330 (about thirty small ops)
+ *           H3DBboxHead.get_targets_single under multi_apply
+ *           mmdet3d/models/roi_heads/bbox_heads/h3d_bbox_head.py:761-932 (per sample: three
+ *           chamfer_distance calls that expand [1, N, M, 3], two get_surface_line_center
+ *           calls, about sixty small ops, seven of them boolean-mask assignments)
+ *
+ * Boxes are rows (cx, cy, cz, sx, sy, sz, yaw) with the GRAVITY centre.
+ *
+ * msmd_box_cue_centers_f32: surface row b * 6 + f (f: +z, -z, +y, -y, +x, -x) and line row
+ * b * 12 + l (the order of depth_box3d.py:305-308) = centre[b] + Rz(-yaw[r % n]) (offset *
+ * size[b] / 2), r the row's own number and n the number of boxes of the call.  r % n, not b, is
+ * the reference's: it repeats its n rotation matrices 6 (12) times against box-major rows.
+ * With every yaw 0 the two readings agree.  Double arithmetic on the float32 inputs, one
+ * rounding per coordinate.  msmd_box_cue_centers_bwd_f32 gives the gradient of the seven
+ * columns: one lane per box gathers its 18 rows (centre, sizes) and the 6 + 12 rows
+ * r = b (mod n) it rotates (yaw), in ascending order, without atomics.
+ *
+ * msmd_h3d_cue_targets_f32: every output of H3DBboxHead.get_targets for the batch in one
+ * launch, nothing read back.  Sample b has gt_counts[b] boxes in gt_boxes[b] (device int32; a
+ * count outside 1 .. max_gt is clipped into it -- an empty sample is the reference's single
+ * zero box with label 0, which is what zero padding holds).  Per (sample, proposal p, cue):
+ *   the nearest ground-truth centre to aggregated[b, p] (squared L2, torch.min's rule: lowest
+ *   index on ties, the first NaN wins -- the selection of msmd_chamfer_fwd_f32, bit for bit);
+ *   that box's cue centre as above with n = the sample's count -> obj_surface_line_center;
+ *   the nearest predicted surface (cues 0-5) or line (cues 6-17) centre to it, same rule;
+ *   the argmax of that primitive's class scores (lowest index among maxima, NaN is a maximum);
+ *   d_center = sqrt(d2 + 1e-6) and likewise d_prim (cue centre to selected primitive) and
+ *   d_own (the proposal's own cue centre, surface_obj / line_obj, to the selected primitive);
+ *   label = d_own < label_*_threshold && d_prim < mask_*_threshold;
+ *   sem = label && argmax == gt_labels[nearest];  near = d_center < near_threshold;
+ *   cues_objectness_label = label, cues_sem_label = sem (both BEFORE the reference's in-place
+ *   multiplication), cues_matching_label = label * near, cues_mask = proposal_objectness_mask =
+ *   near || d_center > far_threshold, proposal_objectness_label = near, cues_match_mask = any
+ *   of the proposal's 18 unmultiplied labels.
+ * Cue rows are the reference's: surface f * P + p, line 6 P + l * P + p; surface_obj is
+ * [B, 6 P, 3] and line_obj [B, 12 P, 3] in that order (the two halves of the [B, 18 P, 3]
+ * cue centres the head's forward leaves).  No atomics, one writer per element, bitwise
+ * reproducible.  No workspace.
+ * Null pointers, a negative size, max_gt / num_surface / num_line / num_classes < 1 (with work
+ * to do) and a NaN threshold return MSMD_ERR_INVALID_ARG; num_classes > 4096 or an element
+ * count that does not fit 31 bits MSMD_ERR_RANGE.  batch == 0 or num_proposals == 0: ok.
+ *
+ * Deviation of the Python head that calls these (h3d_head.H3DBboxHead.loss): the reference
+ * unpacks 13 rpn targets (:348-351) where VoteHead.get_targets returns 14, so its
+ * H3DNet.forward_train raises as written; the head here takes 13 or 14 and drops
+ * assigned_center_targets, the eighth, when 14 arrive.
+ * ------------------------------------------------------------------------ */
+int msmd_h3d_cue_gt_chunk(void);   /* ground-truth centres per LDS chunk */
+int msmd_h3d_cue_pred_chunk(void); /* predicted centres per LDS chunk */
+int msmd_h3d_cue_proposals(void);  /* proposals per workgroup */
+int msmd_box_cue_centers_f32(const float* boxes /* [n,7] */, int n,
+                             float* surface /* [n*6,3] */, float* line /* [n*12,3] */,
+                             msmd_stream_t stream);
+int msmd_box_cue_centers_bwd_f32(const float* boxes /* [n,7] */, int n,
+                                 const float* grad_surface /* [n*6,3] */,
+                                 const float* grad_line /* [n*12,3] */,
+                                 float* grad_boxes /* [n,7] */, msmd_stream_t stream);
+int msmd_h3d_cue_targets_f32(const float* aggregated /* [B,P,3] */,
+                             const float* gt_boxes /* [B,G,7] */,
+                             const int32_t* gt_counts /* [B] */,
+                             const int64_t* gt_labels /* [B,G] */,
+                             const float* surface_pred /* [B,Ns,3] */,
+                             const float* line_pred /* [B,Nl,3] */,
+                             const float* surface_sem /* [B,Ns,C] */,
+                             const float* line_sem /* [B,Nl,C] */,
+                             const float* surface_obj /* [B,6P,3] */,
+                             const float* line_obj /* [B,12P,3] */, int batch,
+                             int num_proposals, int max_gt, int num_surface, int num_line,
+                             int num_classes, float near_threshold, float far_threshold,
+                             float label_surface_threshold, float label_line_threshold,
+                             float mask_surface_threshold, float mask_line_threshold,
+                             int64_t* cues_objectness_label /* [B,18P] */,
+                             int64_t* cues_sem_label /* [B,18P] */,
+                             int64_t* cues_matching_label /* [B,18P] */,
+                             float* cues_mask /* [B,18P] */,
+                             int64_t* proposal_objectness_label /* [B,P] */,
+                             float* proposal_objectness_mask /* [B,P] */,
+                             float* cues_match_mask /* [B,P] */,
+                             float* obj_surface_line_center /* [B,18P,3] */,
+                             msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -265,6 +265,12 @@ SIGNATURES = {
     "msmd_primitive_index": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "msmd_primitive_targets_f32": (_i, [_vp, _i, _vp, _vp, _vp, _vp] + [_i] * 8 + [_f, _f, _f, _i,
                                         _i, _f, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "msmd_h3d_cue_gt_chunk": (_i, []),
+    "msmd_h3d_cue_pred_chunk": (_i, []),
+    "msmd_h3d_cue_proposals": (_i, []),
+    "msmd_box_cue_centers_f32": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "msmd_box_cue_centers_bwd_f32": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "msmd_h3d_cue_targets_f32": (_i, [_vp] * 10 + [_i] * 6 + [_f] * 6 + [_vp] * 9),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -667,7 +667,7 @@ MVXNET_DV_SECOND_KITTI = dict(
 
 # ------------------------------------------------------------------------------- H3DNet (front)
 # configs/_base_/models/h3dnet.py: the four-stream backbone and the three primitive heads of
-# the ScanNet model (the RoI head that consumes them is not built yet)
+# the ScanNet model (H3DNET_SCANNET below is the whole model)
 H3DNET_SCANNET_BACKBONE = dict(
     type="MultiBackbone", num_streams=4, suffixes=["net0", "net1", "net2", "net3"],
     conv_cfg=dict(type="Conv1d"), norm_cfg=dict(type="BN1d", eps=1e-5, momentum=0.01),
@@ -706,3 +706,70 @@ def _h3dnet_primitive(mode, num_dims, side_weight, sem_weight):
 H3DNET_PRIMITIVE_Z = _h3dnet_primitive("z", 2, 0.5, 1.0)
 H3DNET_PRIMITIVE_XY = _h3dnet_primitive("xy", 1, 0.5, 1.0)
 H3DNET_PRIMITIVE_LINE = _h3dnet_primitive("line", 0, 1.0, 2.0)
+
+
+# ------------------------------------------------------------------------------ H3DNet (whole)
+# configs/_base_/models/h3dnet.py merged with configs/h3dnet/h3dnet_3x8_scannet-3d-18class.py:
+# the rpn VoteHead, H3DRoIHead with its H3DBboxHead and the two-stage train_cfg / test_cfg.
+# tests/golden/reference_h3dnet_model_config.json holds the reference's values.
+def _h3dnet_scannet():
+    ce = lambda weight, **kw: dict(type="CrossEntropyLoss", reduction="sum",  # noqa: E731
+                                   loss_weight=weight, **kw)
+    coder = dict(type="PartialBinBasedBBoxCoder", num_sizes=18, num_dir_bins=24, with_rot=False,
+                 mean_sizes=_SCANNET_MEAN_SIZES)
+    center = dict(type="ChamferDistance", mode="l2", reduction="sum", loss_src_weight=10.0,
+                  loss_dst_weight=10.0)
+    smooth = dict(type="SmoothL1Loss", reduction="sum", loss_weight=10.0)
+    matching = lambda rows: dict(                                             # noqa: E731
+        type="PointSAModule", num_point=256 * rows, radius=0.5, num_sample=32,
+        mlp_channels=[128 + rows, 128, 64, 32], use_xyz=True, normalize_xyz=True)
+    cues = lambda weights, reduction: dict(type="CrossEntropyLoss",           # noqa: E731
+                                           class_weight=weights, reduction=reduction,
+                                           loss_weight=5.0)
+    rpn_head = dict(
+        type="VoteHead",
+        vote_module_cfg=dict(
+            in_channels=256, vote_per_seed=1, gt_per_seed=3, conv_channels=(256, 256),
+            conv_cfg=dict(type="Conv1d"), norm_cfg=dict(type="BN1d"), norm_feats=True,
+            vote_loss=dict(type="ChamferDistance", mode="l1", reduction="none",
+                           loss_dst_weight=10.0)),
+        vote_aggregation_cfg=dict(
+            type="PointSAModule", num_point=256, radius=0.3, num_sample=16,
+            mlp_channels=[256, 128, 128, 128], use_xyz=True, normalize_xyz=True),
+        pred_layer_cfg=dict(in_channels=128, shared_conv_channels=(128, 128), bias=True),
+        conv_cfg=dict(type="Conv1d"), norm_cfg=dict(type="BN1d"),
+        objectness_loss=ce(5.0, class_weight=[0.2, 0.8]), center_loss=dict(center),
+        dir_class_loss=ce(1.0), dir_res_loss=dict(smooth), size_class_loss=ce(1.0),
+        size_res_loss=dict(smooth), semantic_loss=ce(1.0), num_classes=18,
+        bbox_coder=dict(coder))
+    bbox_head = dict(
+        type="H3DBboxHead", gt_per_seed=3, num_proposal=256,
+        suface_matching_cfg=matching(6), line_matching_cfg=matching(12),
+        feat_channels=(128, 128), primitive_refine_channels=[128, 128, 128], upper_thresh=100.0,
+        surface_thresh=0.5, line_thresh=0.5, conv_cfg=dict(type="Conv1d"),
+        norm_cfg=dict(type="BN1d"),
+        objectness_loss=ce(5.0, class_weight=[0.2, 0.8]), center_loss=dict(center),
+        dir_class_loss=ce(0.1), dir_res_loss=dict(smooth), size_class_loss=ce(0.1),
+        size_res_loss=dict(smooth), semantic_loss=ce(0.1),
+        cues_objectness_loss=cues([0.3, 0.7], "mean"), cues_semantic_loss=cues([0.3, 0.7], "mean"),
+        proposal_objectness_loss=cues([0.2, 0.8], "none"),
+        primitive_center_loss=dict(type="MSELoss", reduction="none", loss_weight=1.0),
+        num_classes=18, bbox_coder=dict(coder))
+    nms = dict(sample_mod="seed", nms_thr=0.25, score_thr=0.05, per_class_proposal=True)
+    return dict(model=dict(
+        type="H3DNet", backbone=H3DNET_SCANNET_BACKBONE, rpn_head=rpn_head,
+        roi_head=dict(type="H3DRoIHead",
+                      primitive_list=[H3DNET_PRIMITIVE_Z, H3DNET_PRIMITIVE_XY,
+                                      H3DNET_PRIMITIVE_LINE],
+                      bbox_head=bbox_head),
+        train_cfg=dict(
+            rpn=dict(pos_distance_thr=0.3, neg_distance_thr=0.6, sample_mod="vote"),
+            rpn_proposal=dict(use_nms=False),
+            rcnn=dict(pos_distance_thr=0.3, neg_distance_thr=0.6, sample_mod="vote",
+                      far_threshold=0.6, near_threshold=0.3, mask_surface_threshold=0.3,
+                      label_surface_threshold=0.3, mask_line_threshold=0.3,
+                      label_line_threshold=0.3)),
+        test_cfg=dict(rpn=dict(nms, use_nms=False), rcnn=dict(nms))))
+
+
+H3DNET_SCANNET = _h3dnet_scannet()

@@ -28,33 +28,17 @@
 // The backward has the same two shapes and costs what the forward costs.
 #include <math.h>
 
+#include "chamfer_common.hpp"
 #include "common.hpp"
 #include "point_in_box.hpp"
 
 namespace msmd {
 namespace {
 
-enum { kL2 = 0, kL1 = 1, kSmoothL1 = 2 };
-
 constexpr int kChamferTile = 256;      // other-set points per LDS tile
 constexpr int kChamferFlatMax = 1024;  // flat shape: at most this many other points per batch
 constexpr int kVoteGtChunk = 64;       // ground truths per LDS chunk
 constexpr int kVoteSlots = 3;          // gt_per_seed of the reference loop (its clamp at 2)
-
-template <int MODE>
-__device__ __forceinline__ float criterion(float q, float r) {
-  const float d = __fsub_rn(q, r);
-  if (MODE == kL2) return __fmul_rn(d, d);
-  const float z = fabsf(d);
-  if (MODE == kL1) return z;
-  return z < 1.f ? __fmul_rn(__fmul_rn(0.5f, z), z) : __fsub_rn(z, 0.5f);
-}
-
-template <int MODE>
-__device__ __forceinline__ float distance(const float* q, const float* r) {
-  return __fadd_rn(__fadd_rn(criterion<MODE>(q[0], r[0]), criterion<MODE>(q[1], r[1])),
-                   criterion<MODE>(q[2], r[2]));
-}
 
 // the criterion's derivative in d = q - r
 template <int MODE>
@@ -63,14 +47,6 @@ __device__ __forceinline__ float slope(float d) {
   const float sign = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
   if (MODE == kL1) return sign;
   return fabsf(d) < 1.f ? d : sign;
-}
-
-// torch.min: strictly smaller replaces; the first NaN replaces anything that is not NaN
-__device__ __forceinline__ void take_min(float d, int j, float& best, int& at) {
-  if (d < best || (d != d && best == best)) {
-    best = d;
-    at = j;
-  }
 }
 
 // grid: batches * ceil(nq / 64) wavefronts

@@ -469,6 +469,74 @@ class SSD3DNet(VoteNet):
     SSD3DHead."""
 
 
+@DETECTORS.register_module()
+class H3DNet(nn.Module):
+    """mmdet3d/models/detectors/h3dnet.py on two_stage.py (TwoStage3DDetector): MultiBackbone,
+    VoteHead as `rpn_head` (built with train_cfg.rpn / test_cfg.rpn) and H3DRoIHead as
+    `roi_head` (train_cfg.rcnn / test_cfg.rcnn), under the reference's attribute names.
+    aug_test is not built, as for the other detectors."""
+
+    def __init__(self, backbone, neck=None, rpn_head=None, roi_head=None, train_cfg=None,
+                 test_cfg=None, pretrained=None, init_cfg=None):
+        super().__init__()
+        from .registry import build_head
+        if neck is not None:
+            raise NotImplementedError("H3DNet has no neck")
+        sub = lambda cfg, key: None if cfg is None else cfg[key]              # noqa: E731
+        self.backbone = build_backbone(backbone)
+        self.rpn_head = rpn_head if isinstance(rpn_head, nn.Module) else build_head(
+            dict(rpn_head, train_cfg=sub(train_cfg, "rpn"), test_cfg=sub(test_cfg, "rpn")))
+        self.roi_head = roi_head if isinstance(roi_head, nn.Module) else build_head(
+            dict(roi_head, train_cfg=sub(train_cfg, "rcnn"), test_cfg=sub(test_cfg, "rcnn")))
+        self.train_cfg, self.test_cfg = train_cfg, test_cfg
+
+    _stack = staticmethod(VoteNet._stack)
+
+    def extract_feat(self, points, img_metas=None):
+        """h3dnet.py:59-62: the backbone's dictionary, with the names VoteHead reads aliased to
+        the first stream's seeds and the fused feature."""
+        feats_dict = self.backbone(points)
+        feats_dict["fp_xyz"] = [feats_dict["fp_xyz_net0"][-1]]
+        feats_dict["fp_features"] = [feats_dict["hd_feature"]]
+        feats_dict["fp_indices"] = [feats_dict["fp_indices_net0"][-1]]
+        return feats_dict
+
+    def forward_train(self, points, img_metas=None, gt_bboxes_3d=None, gt_labels_3d=None,
+                      pts_semantic_mask=None, pts_instance_mask=None, gt_bboxes_ignore=None):
+        """h3dnet.py:32-96 -> the losses of the rpn head and of the RoI head."""
+        points_cat = self._stack(points)
+        feats_dict = self.extract_feat(points_cat)
+        rpn_outs = self.rpn_head(feats_dict, self.train_cfg["rpn"]["sample_mod"])
+        feats_dict.update(rpn_outs)
+        losses = self.rpn_head.loss(rpn_outs, points_cat, gt_bboxes_3d, gt_labels_3d,
+                                    pts_semantic_mask, pts_instance_mask, img_metas,
+                                    gt_bboxes_ignore=gt_bboxes_ignore, ret_target=True)
+        feats_dict["targets"] = losses.pop("targets")
+        proposal_cfg = self.train_cfg.get("rpn_proposal", self.test_cfg["rpn"])
+        feats_dict["proposal_list"] = self.rpn_head.get_bboxes(
+            points_cat, rpn_outs, img_metas, use_nms=proposal_cfg["use_nms"])
+        losses.update(self.roi_head.forward_train(
+            feats_dict, img_metas, points_cat, gt_bboxes_3d, gt_labels_3d, pts_semantic_mask,
+            pts_instance_mask, gt_bboxes_ignore))
+        return losses
+
+    def simple_test(self, points, img_metas=None, imgs=None, rescale=False):
+        """h3dnet.py:98-128."""
+        points_cat = self._stack(points)
+        feats_dict = self.extract_feat(points_cat)
+        proposal_cfg = self.test_cfg["rpn"]
+        rpn_outs = self.rpn_head(feats_dict, proposal_cfg["sample_mod"])
+        feats_dict.update(rpn_outs)
+        feats_dict["proposal_list"] = self.rpn_head.get_bboxes(
+            points_cat, rpn_outs, img_metas, use_nms=proposal_cfg["use_nms"])
+        return self.roi_head.simple_test(feats_dict, img_metas, points_cat, rescale=rescale)
+
+    def forward(self, points, img_metas=None, return_loss=False, **kw):
+        if return_loss:
+            return self.forward_train(points, img_metas, **kw)
+        return self.simple_test(points, img_metas, **kw)
+
+
 class MLP(nn.Module):
     """mmdet3d/models/utils/mlp.py: (B, C, N) features through kernel-size-1 ConvModules with a
     conv bias under the norm, keys `mlp.layer{i}.conv.*` / `mlp.layer{i}.bn.*`."""

@@ -148,6 +148,28 @@ class LiDARBoxes:
         return LiDARBoxes(self.tensor.to(device), with_yaw=self.with_yaw)
 
 
+_SURFACE_OFFSETS = ((0, 0, 1), (0, 0, -1), (0, 1, 0), (0, -1, 0), (1, 0, 0), (-1, 0, 0))
+_LINE_OFFSETS = ((1, 0, 1), (-1, 0, 1), (0, 1, 1), (0, -1, 1), (1, 0, -1), (-1, 0, -1),
+                 (0, 1, -1), (0, -1, -1), (1, 1, 0), (1, -1, 0), (-1, 1, 0), (-1, -1, 0))
+
+
+def surface_line_center_torch(center, dims, yaw):
+    """get_surface_line_center (depth_box3d.py:277-330) in plain torch, any dtype: gravity
+    centres [G, 3], sizes [G, 3], yaws [G] -> ([G * 6, 3], [G * 12, 3])."""
+    n = center.shape[0]
+    rot_sin, rot_cos = torch.sin(-yaw), torch.cos(-yaw)
+    out = []
+    for offsets in (_SURFACE_OFFSETS, _LINE_OFFSETS):
+        k = len(offsets)
+        offset = torch.tensor(offsets, dtype=dims.dtype, device=dims.device).view(1, k, 3) / 2
+        local = (offset * dims.view(n, 1, 3)).reshape(-1, 3)
+        sin, cos = rot_sin.repeat(k), rot_cos.repeat(k)      # row r: box r % n
+        turned = torch.stack((cos * local[:, 0] - sin * local[:, 1],
+                              sin * local[:, 0] + cos * local[:, 1], local[:, 2]), dim=1)
+        out.append(center.view(n, 1, 3).repeat(1, k, 1).reshape(-1, 3) + turned)
+    return out[0], out[1]
+
+
 class DepthBoxes:
     """What VoteHead reads of DepthInstance3DBoxes (core/bbox/structures/depth_box3d.py,
     base_box3d.py): `.tensor` [G, 7] = (x, y, z_bottom, x_size, y_size, z_size, yaw) in depth
@@ -170,9 +192,9 @@ class DepthBoxes:
             self.box_dim, self.with_yaw = box_dim, with_yaw
         self.tensor = tensor.clone()
         if tuple(origin) != (0.5, 0.5, 0):
-            dst = self.tensor.new_tensor((0.5, 0.5, 0))
-            src = self.tensor.new_tensor(origin)
-            self.tensor[:, :3] += self.tensor[:, 3:6] * (dst - src)
+            # (_constant, not new_tensor: H3DBboxHead's loss calls this and must not block)
+            shift = _constant(self.tensor, [0.5 - origin[0], 0.5 - origin[1], 0.0 - origin[2]])
+            self.tensor[:, :3] += self.tensor[:, 3:6] * shift
 
     def __len__(self):
         return self.tensor.shape[0]
@@ -215,6 +237,22 @@ class DepthBoxes:
         corners = torch.einsum("aij,jka->aik", (corners, rot_mat_t))
         corners += self.tensor[:, :3].view(-1, 1, 3)
         return corners
+
+    @property
+    def yaw(self):
+        return self.tensor[:, 6]
+
+    def get_surface_line_center(self):
+        """depth_box3d.py:277-330 -> (surface_center [G * 6, 3], line_center [G * 12, 3]), rows
+        box-major.  The reference's quirk is kept: row r is turned by the yaw of box r % G (its
+        rot_mat_T.repeat(6, 1, 1) against box-major rows), by the angle -yaw.  Device tensors
+        run msmd_box_cue_centers_f32 (differentiable in centre, sizes and yaw); CPU tensors take
+        the plain-torch form below, which the golden vectors pin."""
+        if self.tensor.is_cuda:
+            from . import kernels as K
+            boxes = torch.cat((self.gravity_center, self.dims, self.yaw[:, None]), dim=1)
+            return K.box_cue_centers(boxes.float())           # the kernels are float32
+        return surface_line_center_torch(self.gravity_center, self.dims, self.yaw)
 
     def new_box(self, data):
         new_tensor = self.tensor.new_tensor(data) if not isinstance(data, torch.Tensor) \

@@ -3660,3 +3660,117 @@ def primitive_targets(points, pts_semantic_mask, point_offsets, corners, box_off
         float(train_cfg["line_thresh"]), bound, _p(index), index.numel(), _p(mask), _p(offset),
         _p(sem), _stream()), "msmd_primitive_targets_f32")
     return mask, offset, sem
+
+
+# ------------------------------------------------------------------ H3DNet second stage (row n8)
+H3D_CUE_GT_CHUNK = lib.msmd_h3d_cue_gt_chunk()
+H3D_CUE_PRED_CHUNK = lib.msmd_h3d_cue_pred_chunk()
+H3D_CUE_PROPOSALS = lib.msmd_h3d_cue_proposals()
+H3D_CUE_THRESHOLDS = ("near_threshold", "far_threshold", "label_surface_threshold",
+                      "label_line_threshold", "mask_surface_threshold", "mask_line_threshold")
+H3D_CUE_TARGET_NAMES = ("cues_objectness_label", "cues_sem_label", "proposal_objectness_label",
+                        "cues_mask", "cues_match_mask", "proposal_objectness_mask",
+                        "cues_matching_label", "obj_surface_line_center")
+
+
+def _need_boxes7(boxes):
+    _need_cuda(boxes)
+    _need_dtype(boxes, torch.float32, "boxes")
+    if boxes.dim() != 2 or boxes.shape[1] != 7 or not boxes.is_contiguous():
+        raise ValueError("boxes must be a contiguous float32 [n, 7] tensor, got %s"
+                         % (tuple(boxes.shape),))
+    return boxes.shape[0]
+
+
+def box_cue_centers_forward(boxes):
+    """boxes float32 [n, 7] = (gravity centre, sizes, yaw) -> (surface [n * 6, 3], line
+    [n * 12, 3]): get_surface_line_center (depth_box3d.py:277-330), its rotation-index quirk
+    included (msmd_box_cue_centers_f32)."""
+    n = _need_boxes7(boxes)
+    surface = torch.empty((n * 6, 3), dtype=torch.float32, device=boxes.device)
+    line = torch.empty((n * 12, 3), dtype=torch.float32, device=boxes.device)
+    check(lib.msmd_box_cue_centers_f32(_p(boxes), n, _p(surface), _p(line), _stream()),
+          "msmd_box_cue_centers_f32")
+    return surface, line
+
+
+def box_cue_centers_backward(boxes, grad_surface, grad_line):
+    """-> grad_boxes [n, 7] for upstream [n * 6, 3] and [n * 12, 3]; fixed order, no atomics."""
+    n = _need_boxes7(boxes)
+    _need_cuda(grad_surface, grad_line)
+    for t, rows, what in ((grad_surface, n * 6, "grad_surface"), (grad_line, n * 12, "grad_line")):
+        _need_dtype(t, torch.float32, what)
+        if tuple(t.shape) != (rows, 3) or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float32 [%d, 3] tensor" % (what, rows))
+    grad = torch.empty_like(boxes)
+    check(lib.msmd_box_cue_centers_bwd_f32(_p(boxes), n, _p(grad_surface), _p(grad_line),
+                                           _p(grad), _stream()), "msmd_box_cue_centers_bwd_f32")
+    return grad
+
+
+class _BoxCueCenters(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, boxes):
+        boxes = boxes.contiguous()
+        ctx.save_for_backward(boxes)
+        return box_cue_centers_forward(boxes)
+
+    @staticmethod
+    def backward(ctx, grad_surface, grad_line):
+        boxes, = ctx.saved_tensors
+        n = boxes.shape[0]
+        gs = boxes.new_zeros((n * 6, 3)) if grad_surface is None else grad_surface.contiguous()
+        gl = boxes.new_zeros((n * 12, 3)) if grad_line is None else grad_line.contiguous()
+        return box_cue_centers_backward(boxes, gs, gl)
+
+
+def box_cue_centers(boxes):
+    """box_cue_centers_forward, differentiable in all seven columns."""
+    return _BoxCueCenters.apply(boxes)
+
+
+def h3d_cue_targets(aggregated, gt_boxes, gt_counts, gt_labels, surface_pred, line_pred,
+                    surface_sem, line_sem, surface_obj, line_obj, train_cfg):
+    """H3DBboxHead.get_targets_single (h3d_bbox_head.py:761-932) for every sample in one launch
+    (msmd_h3d_cue_targets_f32), nothing read back.  aggregated [B, P, 3]; gt_boxes [B, G, 7]
+    in gravity-centre form, zero padded, with gt_counts int32 [B] and gt_labels long [B, G];
+    surface_pred [B, Ns, 3], line_pred [B, Nl, 3] with scores [B, Ns, C], [B, Nl, C];
+    surface_obj [B, 6 P, 3] and line_obj [B, 12 P, 3], the proposals' own cue centres;
+    train_cfg holds H3D_CUE_THRESHOLDS.  -> the reference's eight results stacked, in its
+    order (H3D_CUE_TARGET_NAMES)."""
+    floats = ((aggregated, "aggregated"), (gt_boxes, "gt_boxes"), (surface_pred, "surface_pred"),
+              (line_pred, "line_pred"), (surface_sem, "surface_sem"), (line_sem, "line_sem"),
+              (surface_obj, "surface_obj"), (line_obj, "line_obj"))
+    _need_cuda(gt_counts, gt_labels, *[t for t, _ in floats])
+    for t, what in floats:
+        _need_dtype(t, torch.float32, what)
+        if t.dim() != 3 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float32 [B, N, C] tensor, got %s"
+                             % (what, tuple(t.shape)))
+    _need_dtype(gt_counts, torch.int32, "gt_counts")
+    _need_dtype(gt_labels, torch.long, "gt_labels")
+    b, p = aggregated.shape[:2]
+    g, ns, nl, c = gt_boxes.shape[1], surface_pred.shape[1], line_pred.shape[1], \
+        surface_sem.shape[2]
+    want = ((aggregated, (b, p, 3)), (gt_boxes, (b, g, 7)), (surface_pred, (b, ns, 3)),
+            (line_pred, (b, nl, 3)), (surface_sem, (b, ns, c)), (line_sem, (b, nl, c)),
+            (surface_obj, (b, 6 * p, 3)), (line_obj, (b, 12 * p, 3)), (gt_labels, (b, g)),
+            (gt_counts, (b,)))
+    for t, shape in want:
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError("h3d_cue_targets: expected a contiguous %s tensor, got %s"
+                             % (shape, tuple(t.shape)))
+    dev = aggregated.device
+    f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)       # noqa: E731
+    l = lambda *shape: torch.empty(shape, dtype=torch.long, device=dev)          # noqa: E731,E741
+    obj_label, sem_label, match_label, cues_mask = l(b, 18 * p), l(b, 18 * p), l(b, 18 * p), \
+        f(b, 18 * p)
+    prop_label, prop_mask, match_mask, centers = l(b, p), f(b, p), f(b, p), f(b, 18 * p, 3)
+    check(lib.msmd_h3d_cue_targets_f32(
+        _p(aggregated), _p(gt_boxes), _p(gt_counts), _p(gt_labels), _p(surface_pred),
+        _p(line_pred), _p(surface_sem), _p(line_sem), _p(surface_obj), _p(line_obj), b, p, g, ns,
+        nl, c, *[float(train_cfg[k]) for k in H3D_CUE_THRESHOLDS], _p(obj_label), _p(sem_label),
+        _p(match_label), _p(cues_mask), _p(prop_label), _p(prop_mask), _p(match_mask),
+        _p(centers), _stream()), "msmd_h3d_cue_targets_f32")
+    return (obj_label, sem_label, prop_label, cues_mask, match_mask, prop_mask, match_label,
+            centers)

@@ -140,8 +140,9 @@ class CrossEntropyLoss(nn.Module):
                 **kwargs):
         assert reduction_override in (None, "none", "mean", "sum")
         reduction = reduction_override if reduction_override else self.reduction
-        class_weight = None if self.class_weight is None else \
-            cls_score.new_tensor(self.class_weight)
+        # (uploaded without blocking: Tensor.new_tensor on a device tensor is a blocking copy)
+        class_weight = None if self.class_weight is None else torch.tensor(
+            self.class_weight, dtype=cls_score.dtype).to(cls_score.device, non_blocking=True)
         if weight is not None:
             weight = weight.float()
         if self.use_sigmoid:
@@ -176,13 +177,30 @@ class SmoothL1Loss(nn.Module):
         return self.loss_weight * weight_reduce_loss(loss, weight, reduction, avg_factor)
 
 
+class MSELoss(nn.Module):
+    """mmdet MSELoss (mse_loss under weighted_loss): the element-wise squared error, then
+    weight, reduction / avg_factor, loss_weight.  H3DBboxHead's cues_semantic_loss uses
+    reduction='none' with a weight."""
+
+    def __init__(self, reduction="mean", loss_weight=1.0):
+        super().__init__()
+        self.reduction, self.loss_weight = reduction, loss_weight
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None,
+                **kwargs):
+        assert reduction_override in (None, "none", "mean", "sum")
+        reduction = reduction_override if reduction_override else self.reduction
+        loss = F.mse_loss(pred, target, reduction="none")
+        return self.loss_weight * weight_reduce_loss(loss, weight, reduction, avg_factor)
+
+
 _LOSSES = {"ChamferDistance": ChamferDistance, "CrossEntropyLoss": CrossEntropyLoss,
-           "SmoothL1Loss": SmoothL1Loss}
+           "SmoothL1Loss": SmoothL1Loss, "MSELoss": MSELoss}
 
 
 def build_loss(cfg):
-    """dict(type='ChamferDistance' | 'CrossEntropyLoss' | 'SmoothL1Loss', ...) -> the module (the
-    LOSSES registry entries the VoteNet configs name)."""
+    """dict(type='ChamferDistance' | 'CrossEntropyLoss' | 'SmoothL1Loss' | 'MSELoss', ...) -> the
+    module (the LOSSES registry entries the VoteNet and H3DNet configs name)."""
     if not isinstance(cfg, dict):
         return cfg
     args = dict(cfg)

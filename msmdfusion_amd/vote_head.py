@@ -433,6 +433,62 @@ def instance_vote_targets(points, pts_semantic_mask, pts_instance_mask, num_clas
 
 
 # ------------------------------------------------------------------------------------- head
+def multiclass_nms_batch(obj_scores, sem_scores, bbox3d, points, with_yaw, test_cfg):
+    """multiclass_nms_single (vote_head.py:614-666, h3d_bbox_head.py:492-550) for the whole batch:
+    objectness [B, P], class scores [B, P, C], decoded boxes [B, P, 7] (gravity centre) and points
+    [B, N, >= 3] -> a list of (DepthBoxes, scores, labels) per sample.  test_cfg holds nms_thr,
+    score_thr and per_class_proposal.  VoteHead and H3DBboxHead share it."""
+    if not torch.is_tensor(points):
+        points = torch.stack(list(points))
+    batch, proposals = bbox3d.shape[:2]
+    device = bbox3d.device
+    # the decoded centre is the gravity centre
+    boxes = DepthBoxes(bbox3d.reshape(batch * proposals, -1), box_dim=bbox3d.shape[-1],
+                       with_yaw=with_yaw, origin=(0.5, 0.5, 0.5))
+    count = K.points_in_boxes_count(
+        DepthBoxes.boxes_to_lidar(boxes.tensor).view(batch, proposals, 7).contiguous(),
+        DepthBoxes.points_to_lidar(points.float()).contiguous())
+    nonempty = (count > 5).reshape(-1)
+    corner3d = boxes.corners
+    minmax_box3d = torch.cat([torch.min(corner3d, dim=1)[0], torch.max(corner3d, dim=1)[0]], 1)
+    bbox_classes = torch.argmax(sem_scores, -1).reshape(-1)
+    flat_scores = obj_scores.reshape(-1)
+
+    # one NMS call.  Rows in (non-empty first, sample, descending score) order; the segment of
+    # sample b covers its non-empty boxes only, the empty ones lie past the last segment.
+    sample = torch.arange(batch, device=device).repeat_interleave(proposals)
+    by_score = torch.sort(flat_scores, descending=True, stable=True)[1]
+    key = torch.where(nonempty, sample, sample + batch)[by_score]
+    order = by_score[torch.sort(key, stable=True)[1]]
+    offsets = torch.cat([count.new_zeros(1, dtype=torch.long),
+                         torch.cumsum(nonempty.view(batch, proposals).sum(1), 0)]).int()
+    rows = torch.cat([minmax_box3d, bbox_classes.float()[:, None]], 1)[order].contiguous()
+    thresh = torch.full((batch,), float(_cfg_get(test_cfg, "nms_thr")),
+                        dtype=torch.float32, device=device)
+    keep, _ = K.nms_segments("aligned3d", rows, offsets, thresh, proposals, order=order)
+    nms_mask = torch.zeros(batch * proposals + 1, dtype=torch.bool, device=device)
+    nms_mask[(keep + 1).reshape(-1)] = True                      # -1 lands in the spare slot
+    selected = nms_mask[1:] & (flat_scores > _cfg_get(test_cfg, "score_thr"))
+
+    chosen = selected.view(batch, proposals).cpu()               # the one host read
+    results = []
+    per_class = _cfg_get(test_cfg, "per_class_proposal")
+    for b in range(batch):
+        index = (torch.nonzero(chosen[b]).flatten() + b * proposals).to(device)
+        box_b, obj_b = boxes.tensor[index], flat_scores[index]
+        if per_class:
+            sem_b = sem_scores.reshape(batch * proposals, -1)[index]
+            classes = sem_b.shape[-1]
+            bbox_selected = box_b.repeat(classes, 1)
+            score_selected = (obj_b[None, :] * sem_b.t()).reshape(-1)
+            labels = torch.arange(classes, device=device).repeat_interleave(index.numel())
+        else:
+            bbox_selected, score_selected, labels = box_b, obj_b, bbox_classes[index]
+        results.append((DepthBoxes(bbox_selected, box_dim=bbox_selected.shape[-1],
+                                   with_yaw=with_yaw), score_selected, labels))
+    return results
+
+
 @HEADS.register_module()
 class VoteHead(nn.Module):
     """vote_head.py: votes from the seeds, a set-abstraction layer over the votes, the
@@ -672,53 +728,5 @@ class VoteHead(nn.Module):
         bbox3d = self.bbox_coder.decode(bbox_preds)
         if not use_nms:
             return bbox3d
-        if not torch.is_tensor(points):
-            points = torch.stack(list(points))
-        batch, proposals = bbox3d.shape[:2]
-        device = bbox3d.device
-        with_yaw = self.bbox_coder.with_rot
-        # the decoded centre is the gravity centre
-        boxes = DepthBoxes(bbox3d.reshape(batch * proposals, -1), box_dim=bbox3d.shape[-1],
-                           with_yaw=with_yaw, origin=(0.5, 0.5, 0.5))
-        count = K.points_in_boxes_count(
-            DepthBoxes.boxes_to_lidar(boxes.tensor).view(batch, proposals, 7).contiguous(),
-            DepthBoxes.points_to_lidar(points.float()).contiguous())
-        nonempty = (count > 5).reshape(-1)
-        corner3d = boxes.corners
-        minmax_box3d = torch.cat([torch.min(corner3d, dim=1)[0], torch.max(corner3d, dim=1)[0]], 1)
-        bbox_classes = torch.argmax(sem_scores, -1).reshape(-1)
-        flat_scores = obj_scores.reshape(-1)
-
-        # one NMS call.  Rows in (non-empty first, sample, descending score) order; the segment of
-        # sample b covers its non-empty boxes only, the empty ones lie past the last segment.
-        sample = torch.arange(batch, device=device).repeat_interleave(proposals)
-        by_score = torch.sort(flat_scores, descending=True, stable=True)[1]
-        key = torch.where(nonempty, sample, sample + batch)[by_score]
-        order = by_score[torch.sort(key, stable=True)[1]]
-        offsets = torch.cat([count.new_zeros(1, dtype=torch.long),
-                             torch.cumsum(nonempty.view(batch, proposals).sum(1), 0)]).int()
-        rows = torch.cat([minmax_box3d, bbox_classes.float()[:, None]], 1)[order].contiguous()
-        thresh = torch.full((batch,), float(_cfg_get(self.test_cfg, "nms_thr")),
-                            dtype=torch.float32, device=device)
-        keep, _ = K.nms_segments("aligned3d", rows, offsets, thresh, proposals, order=order)
-        nms_mask = torch.zeros(batch * proposals + 1, dtype=torch.bool, device=device)
-        nms_mask[(keep + 1).reshape(-1)] = True                      # -1 lands in the spare slot
-        selected = nms_mask[1:] & (flat_scores > _cfg_get(self.test_cfg, "score_thr"))
-
-        chosen = selected.view(batch, proposals).cpu()               # the one host read
-        results = []
-        per_class = _cfg_get(self.test_cfg, "per_class_proposal")
-        for b in range(batch):
-            index = (torch.nonzero(chosen[b]).flatten() + b * proposals).to(device)
-            box_b, obj_b = boxes.tensor[index], flat_scores[index]
-            if per_class:
-                sem_b = sem_scores.reshape(batch * proposals, -1)[index]
-                classes = sem_b.shape[-1]
-                bbox_selected = box_b.repeat(classes, 1)
-                score_selected = (obj_b[None, :] * sem_b.t()).reshape(-1)
-                labels = torch.arange(classes, device=device).repeat_interleave(index.numel())
-            else:
-                bbox_selected, score_selected, labels = box_b, obj_b, bbox_classes[index]
-            results.append((DepthBoxes(bbox_selected, box_dim=bbox_selected.shape[-1],
-                                       with_yaw=with_yaw), score_selected, labels))
-        return results
+        return multiclass_nms_batch(obj_scores, sem_scores, bbox3d, points,
+                                    self.bbox_coder.with_rot, self.test_cfg)
