@@ -2055,6 +2055,41 @@ int msmd_h3d_cue_targets_f32(const float* aggregated /* [B,P,3] */,
                              float* obj_surface_line_center /* [B,18P,3] */,
                              msmd_stream_t stream);
 
+/* ---- Part-A2, first stage (COVERAGE n9) ---------------------------------------------------
+ * Semantic and part targets of PointwiseSemanticHead for the whole batch in one launch: what
+ * get_targets / get_targets_single compute per sample
+ * (mmdet3d/models/roi_heads/mask_heads/pointwise_semantic_head.py:78-157: two
+ * points_in_boxes_gpu launches, then per ground-truth box a boolean mask, a host read, a
+ * gather, an einsum rotation and a masked write, and a torch.cat per batch).
+ * Row i is voxel centre voxel_centers[i] of sample batch_ids[i] (coors[:, 0]); rows may be in
+ * any order.  Sample b has gt_counts[b] boxes (device int32, clipped into 0 .. max_gt) in
+ * gt_boxes[b] and enlarged_boxes[b], both in the frame of msmd_points_in_boxes_f32 (LiDAR,
+ * bottom centre) and tested with its predicate; enlarged_boxes is the caller's
+ * LiDARInstance3DBoxes.enlarged_box(extra_width) of gt_boxes.  labels is int64 (labels_int64
+ * = 1) or int32 (0).  Per row, k = the first box of its sample holding the centre, or none:
+ *   seg_targets  = labels[k] verbatim, num_classes when there is no k; -1 when (a k exists) !=
+ *                  (any enlarged box holds the centre);
+ *   part_targets = max(rot_z(-yaw[k]) (centre - bottom_centre[k]) / dims[k] + (0.5, 0.5, 0), 0)
+ *                  in the row-vector convention of rotation_3d_in_axis(axis=2), float32, one
+ *                  rounding per operation, NaN kept as torch.clamp keeps it; 0 when there is
+ *                  no k.
+ * A row whose batch id is outside [0, batch) gets seg = -1 and part = 0 (the reference drops
+ * such rows).  Output is in input row order, which is the reference's torch.cat whenever the
+ * ids do not decrease.  A NaN centre or box fails the predicate.  Every output element is
+ * written; no atomics, no workspace, nothing read back; the launch shape depends on num_rows
+ * only.  Null pointers (with work to do), a negative size and num_classes < 1 return
+ * MSMD_ERR_INVALID_ARG before anything is enqueued; batch * max_gt * 7 >= 2^31 MSMD_ERR_RANGE.
+ * num_rows == 0, batch == 0 and max_gt == 0 are valid. */
+int msmd_semantic_gt_chunk(void); /* boxes per LDS chunk */
+int msmd_semantic_targets_f32(const float* voxel_centers /* [num_rows,3] */,
+                              const int32_t* batch_ids /* [num_rows] */,
+                              const float* gt_boxes /* [batch,max_gt,7] */,
+                              const float* enlarged_boxes /* [batch,max_gt,7] */,
+                              const void* labels /* [batch,max_gt] */, int labels_int64,
+                              const int32_t* gt_counts /* [batch] */, int num_rows, int batch,
+                              int max_gt, int num_classes, int64_t* seg_targets /* [num_rows] */,
+                              float* part_targets /* [num_rows,3] */, msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

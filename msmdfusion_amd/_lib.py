@@ -271,6 +271,8 @@ SIGNATURES = {
     "msmd_box_cue_centers_f32": (_i, [_vp, _i, _vp, _vp, _vp]),
     "msmd_box_cue_centers_bwd_f32": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "msmd_h3d_cue_targets_f32": (_i, [_vp] * 10 + [_i] * 6 + [_f] * 6 + [_vp] * 9),
+    "msmd_semantic_gt_chunk": (_i, []),
+    "msmd_semantic_targets_f32": (_i, [_vp] * 5 + [_i, _vp] + [_i] * 4 + [_vp] * 3),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

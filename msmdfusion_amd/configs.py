@@ -773,3 +773,93 @@ def _h3dnet_scannet():
 
 
 H3DNET_SCANNET = _h3dnet_scannet()
+
+
+# ---------------------------------------------------------------------------------------------
+# Part-A2 on KITTI (configs/parta2/hv_PartA2_secfpn_2x8_cyclic_80e_kitti-3d-3class.py and
+# -car.py, the second with its _base_ merged): SparseUNet + SECOND / SECONDFPN + PartA2RPNHead,
+# then PartAggregationROIHead with PointwiseSemanticHead.  The roi_head's extractors, its
+# bbox_head and the rcnn entries are data here: PartAggregationROIHead, PartA2BboxHead and the
+# PartA2 detector are not built.  tests/golden/reference_parta2_configs.json holds the
+# reference's values.
+def _parta2_rcnn_assigner():
+    return dict(type="MaxIoUAssigner", iou_calculator=dict(type="BboxOverlaps3D",
+                                                           coordinate="lidar"),
+                pos_iou_thr=0.55, neg_iou_thr=0.55, min_pos_iou=0.55, ignore_iof_thr=-1)
+
+
+def _parta2_roi_extractor(mode):
+    return dict(type="Single3DRoIAwareExtractor",
+                roi_layer=dict(type="RoIAwarePool3d", out_size=14, max_pts_per_voxel=128,
+                               mode=mode))
+
+
+def _parta2(num_classes, anchor_ranges, anchor_sizes, rpn_assigner, rcnn_assigner):
+    return dict(model=dict(
+        type="PartA2",
+        voxel_layer=dict(max_num_points=5, point_cloud_range=[0, -40, -3, 70.4, 40, 1],
+                         voxel_size=[0.05, 0.05, 0.1], max_voxels=(16000, 40000)),
+        voxel_encoder=dict(type="HardSimpleVFE"),
+        middle_encoder=dict(type="SparseUNet", in_channels=4, sparse_shape=[41, 1600, 1408],
+                            order=("conv", "norm", "act")),
+        backbone=dict(type="SECOND", in_channels=256, layer_nums=[5, 5], layer_strides=[1, 2],
+                      out_channels=[128, 256]),
+        neck=dict(type="SECONDFPN", in_channels=[128, 256], upsample_strides=[1, 2],
+                  out_channels=[256, 256]),
+        rpn_head=dict(
+            type="PartA2RPNHead", num_classes=num_classes, in_channels=512, feat_channels=512,
+            use_direction_classifier=True,
+            anchor_generator=dict(type="Anchor3DRangeGenerator", ranges=anchor_ranges,
+                                  sizes=anchor_sizes, rotations=[0, 1.57], reshape_out=False),
+            diff_rad_by_sin=True, assigner_per_size=True, assign_per_class=True,
+            bbox_coder=dict(type="DeltaXYZWLHRBBoxCoder"),
+            loss_cls=dict(type="FocalLoss", use_sigmoid=True, gamma=2.0, alpha=0.25,
+                          loss_weight=1.0),
+            loss_bbox=dict(type="SmoothL1Loss", beta=1.0 / 9.0, loss_weight=2.0),
+            loss_dir=dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=0.2)),
+        roi_head=dict(
+            type="PartAggregationROIHead", num_classes=num_classes,
+            semantic_head=dict(
+                type="PointwiseSemanticHead", in_channels=16, extra_width=0.2, seg_score_thr=0.3,
+                num_classes=num_classes,
+                loss_seg=dict(type="FocalLoss", use_sigmoid=True, reduction="sum", gamma=2.0,
+                              alpha=0.25, loss_weight=1.0),
+                loss_part=dict(type="CrossEntropyLoss", use_sigmoid=True, loss_weight=1.0)),
+            seg_roi_extractor=_parta2_roi_extractor("max"),
+            part_roi_extractor=_parta2_roi_extractor("avg"),
+            bbox_head=dict(
+                type="PartA2BboxHead", num_classes=num_classes, seg_in_channels=16,
+                part_in_channels=4, seg_conv_channels=[64, 64], part_conv_channels=[64, 64],
+                merge_conv_channels=[128, 128], down_conv_channels=[128, 256],
+                bbox_coder=dict(type="DeltaXYZWLHRBBoxCoder"),
+                shared_fc_channels=[256, 512, 512, 512], cls_channels=[256, 256],
+                reg_channels=[256, 256], dropout_ratio=0.1, roi_feat_size=14,
+                with_corner_loss=True,
+                loss_bbox=dict(type="SmoothL1Loss", beta=1.0 / 9.0, reduction="sum",
+                               loss_weight=1.0),
+                loss_cls=dict(type="CrossEntropyLoss", use_sigmoid=True, reduction="sum",
+                              loss_weight=1.0))),
+        train_cfg=dict(
+            rpn=dict(assigner=rpn_assigner, allowed_border=0, pos_weight=-1, debug=False),
+            rpn_proposal=dict(nms_pre=9000, nms_post=512, max_num=512, nms_thr=0.8, score_thr=0,
+                              use_rotate_nms=False),
+            rcnn=dict(assigner=rcnn_assigner,
+                      sampler=dict(type="IoUNegPiecewiseSampler", num=128, pos_fraction=0.55,
+                                   neg_piece_fractions=[0.8, 0.2], neg_iou_piece_thrs=[0.55, 0.1],
+                                   neg_pos_ub=-1, add_gt_as_proposals=False, return_iou=True),
+                      cls_pos_thr=0.75, cls_neg_thr=0.25)),
+        test_cfg=dict(
+            rpn=dict(nms_pre=1024, nms_post=100, max_num=100, nms_thr=0.7, score_thr=0,
+                     use_rotate_nms=True),
+            rcnn=dict(use_rotate_nms=True, use_raw_score=True, nms_thr=0.01, score_thr=0.1))))
+
+
+PARTA2_SECFPN_KITTI_3CLASS = _parta2(
+    3, [[0, -40.0, -0.6, 70.4, 40.0, -0.6], [0, -40.0, -0.6, 70.4, 40.0, -0.6],
+        [0, -40.0, -1.78, 70.4, 40.0, -1.78]],
+    [[0.6, 0.8, 1.73], [0.6, 1.76, 1.73], [1.6, 3.9, 1.56]],
+    [_kitti_assigner(0.5, 0.35), _kitti_assigner(0.5, 0.35), _kitti_assigner(0.6, 0.45)],
+    [_parta2_rcnn_assigner(), _parta2_rcnn_assigner(), _parta2_rcnn_assigner()])
+PARTA2_SECFPN_KITTI_CAR = _parta2(
+    1, [[0, -40.0, -1.78, 70.4, 40.0, -1.78]], [[1.6, 3.9, 1.56]], _kitti_assigner(0.6, 0.45),
+    _parta2_rcnn_assigner())

@@ -3774,3 +3774,46 @@ def h3d_cue_targets(aggregated, gt_boxes, gt_counts, gt_labels, surface_pred, li
         _p(centers), _stream()), "msmd_h3d_cue_targets_f32")
     return (obj_label, sem_label, prop_label, cues_mask, match_mask, prop_mask, match_label,
             centers)
+
+
+# ------------------------------------------------ Part-A2 semantic / part targets (row n9)
+SEMANTIC_GT_CHUNK = lib.msmd_semantic_gt_chunk()
+
+
+def semantic_targets(voxel_centers, batch_ids, gt_boxes, enlarged_boxes, gt_labels, gt_counts,
+                     num_classes):
+    """PointwiseSemanticHead.get_targets (pointwise_semantic_head.py:78-157) for every sample
+    in one launch (msmd_semantic_targets_f32), nothing read back.  voxel_centers float32 [N, 3];
+    batch_ids int32 [N] (coors[:, 0], any order); gt_boxes / enlarged_boxes float32 [B, G, 7]
+    (LiDAR, bottom centre; the second is enlarged_box(extra_width) of the first), gt_labels long
+    or int32 [B, G], gt_counts int32 [B] on the device.
+    -> (seg_targets long [N], part_targets float32 [N, 3]), both written in full by the kernel,
+    in input row order."""
+    _need_cuda(voxel_centers, batch_ids, gt_boxes, enlarged_boxes, gt_labels, gt_counts)
+    for t, what in ((voxel_centers, "voxel_centers"), (gt_boxes, "gt_boxes"),
+                    (enlarged_boxes, "enlarged_boxes")):
+        _need_dtype(t, torch.float32, what)
+    _need_dtype(batch_ids, torch.int32, "batch_ids")
+    _need_dtype(gt_counts, torch.int32, "gt_counts")
+    if gt_labels.dtype not in (torch.long, torch.int32):
+        raise ValueError("gt_labels must be long or int32, got %s" % gt_labels.dtype)
+    if voxel_centers.dim() != 2 or voxel_centers.shape[1] != 3:
+        raise ValueError("voxel_centers must be [N, 3], got %s" % (tuple(voxel_centers.shape),))
+    n = voxel_centers.shape[0]
+    if gt_boxes.dim() != 3 or gt_boxes.shape[2] != 7:
+        raise ValueError("gt_boxes must be [B, G, 7], got %s" % (tuple(gt_boxes.shape),))
+    b, g = gt_boxes.shape[:2]
+    want = ((voxel_centers, (n, 3)), (batch_ids, (n,)), (gt_boxes, (b, g, 7)),
+            (enlarged_boxes, (b, g, 7)), (gt_labels, (b, g)), (gt_counts, (b,)))
+    for t, shape in want:
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError("semantic_targets: expected a contiguous %s tensor, got %s"
+                             % (shape, tuple(t.shape)))
+    dev = voxel_centers.device
+    seg = torch.empty((n,), dtype=torch.long, device=dev)
+    part = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    check(lib.msmd_semantic_targets_f32(
+        _p(voxel_centers), _p(batch_ids), _p(gt_boxes), _p(enlarged_boxes), _p(gt_labels),
+        int(gt_labels.dtype == torch.long), _p(gt_counts), n, b, g, int(num_classes), _p(seg),
+        _p(part), _stream()), "msmd_semantic_targets_f32")
+    return seg, part

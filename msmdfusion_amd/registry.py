@@ -193,11 +193,12 @@ def build_head(cfg, **kwargs):
     """mmdet3d.models.builder.build_head: CenterHead / SeparateHead (center_head.py),
     Anchor3DHead (anchor_head.py), FreeAnchor3DHead (free_anchor_head.py), VoteHead /
     BaseConvBboxHead (vote_head.py), SSD3DHead (ssd3d_head.py), PrimitiveHead
-    (primitive_head.py), H3DBboxHead / H3DRoIHead (h3d_head.py), TransFusionHead (head.py) and,
+    (primitive_head.py), H3DBboxHead / H3DRoIHead (h3d_head.py), PointwiseSemanticHead
+    (semantic_head.py), PartA2RPNHead (parta2_rpn_head.py), TransFusionHead (head.py) and,
     for a TransFusionHead config with fuse_img=True, TransFusionHeadLC (fusion_head.py): the
     reference has one class for both, so its config dicts build unchanged."""
     from . import (anchor_head, center_head, free_anchor_head, fusion_head, h3d_head,  # noqa: F401
-                   head, primitive_head, ssd3d_head, vote_head)
+                   head, parta2_rpn_head, primitive_head, semantic_head, ssd3d_head, vote_head)
     if isinstance(cfg, dict) and cfg.get("type") == "TransFusionHead" and cfg.get("fuse_img"):
         cfg = dict(cfg, type="TransFusionHeadLC")
     return HEADS.build(cfg, **kwargs)
