@@ -2090,6 +2090,89 @@ int msmd_semantic_targets_f32(const float* voxel_centers /* [num_rows,3] */,
                               int max_gt, int num_classes, int64_t* seg_targets /* [num_rows] */,
                               float* part_targets /* [num_rows,3] */, msmd_stream_t stream);
 
+/* ---- Part-A2, second stage (COVERAGE n10) -------------------------------------------------
+ * PartAggregationROIHead._assign_and_sample (mmdet3d/models/roi_heads/
+ * part_aggregation_roi_head.py:222-294) and PartA2BboxHead.get_targets (bbox_heads/
+ * parta2_bbox_head.py:356-460) for every sample of the batch, nothing read back.
+ *
+ * Both calls take the batch as flat lists: proposals [P, 7] and gt_boxes [G, 7] (LiDAR rows x, y,
+ * z_bottom, dx, dy, dz, yaw) with HOST offset tables of batch + 1 ascending entries from 0
+ * (list lengths are tensor shapes; the tables travel by value in the kernel arguments).
+ *
+ * msmd_roi_assign3d_f32: class-aware MaxIoUAssigner (mmdet core/bbox/assigners/
+ * max_iou_assigner.py, gt_max_assign_all = match_low_quality = True, no ignore set) over the
+ * 3-D IoU of BboxOverlaps3D(coordinate='lidar'); the pair value is the one
+ * msmd_boxes_iou3d_f32 writes, bit for bit.  single = 0: an IoU is formed only where
+ * proposal_labels[p] == gt_labels[g] and that label lies in [0, num_classes); thresholds are
+ * per class (host arrays of num_classes floats).  single = 1: no label test, thresholds are
+ * element 0, proposal_labels may be null.  Per proposal:
+ *   gt_inds       -1 ignored, 0 background, i + 1 with i the index in the sample's ground-truth
+ *                 list (the merged convention of :263-275); ties of the arg-max go to the lowest
+ *                 index, of rule 4 (low-quality matches) to the highest, as in the reference;
+ *   max_overlaps  the largest IoU over the ground truths of the proposal's class, 0 when the
+ *                 class has none or the label is outside [0, num_classes);
+ *   labels        gt_labels of the assigned ground truth, else -1.
+ * A row with a NaN coordinate takes part in no pair: a NaN proposal gets gt_inds = -1 and
+ * max_overlaps = NaN, and no other row depends on it.  The per-ground-truth maximum is an
+ * integer atomicMax on the bits of the non-negative IoU, so the result is bitwise reproducible.
+ * Three enqueued operations (memset, two launches).  batch > msmd_roi_assign_max_samples() or
+ * num_classes > msmd_roi_assign_max_classes(): MSMD_ERR_RANGE.
+ *
+ * msmd_roi_sample_targets_f32: IoUNegPiecewiseSampler.sample (core/bbox/samplers/
+ * iou_neg_piecewise_sampler.py, add_gt_as_proposals = False, return_iou = True) followed by
+ * _get_target_single, one workgroup per sample, no atomics, one launch.  random_choice(gallery,
+ * n) is "the n entries with the smallest keys (one float32 per proposal), ties to the lower
+ * proposal index".  Quotas as the reference computes them: int(n * fraction) is (int)((double)
+ * n * fraction); extend_num, the last-piece rule, neg_pos_ub (< 0: none) and both early returns
+ * included.  Piece k holds max_overlaps in [thrs[k+1], thrs[k]) (the last: [0, thrs[k])); the
+ * bounds must not ascend, the fractions of all but the last piece lie in [0, 1] and sum to at
+ * most 1, and num_expected_pos <= num (else MSMD_ERR_INVALID_ARG): that keeps a sample's rows
+ * within `num`.
+ * Outputs are padded to `num` rows per sample: row r of sample s at s * num + r, positives in
+ * ascending proposal order, then negatives in ascending order, then zero rows (sampled_inds
+ * -1).  Per row: rois (s, box), ious, label (1 above cls_pos_thr, 0 below cls_neg_thr, else
+ * iou * 2 - 0.5 in two roundings), label_weights (label >= 0), reg_mask / bbox_weights (1 for
+ * positives), pos_gt_bboxes and bbox_targets (positives; zero otherwise): the canonical
+ * transform of :428-448 and DeltaXYZWLHRBBoxCoder.encode against the zero-centred, zero-yaw
+ * RoI, float32 as written.  counts[s] = (positives, negatives).  Every output element is
+ * written.  More than msmd_roi_sample_max_proposals() proposals in a sample, num >
+ * msmd_roi_sample_max_num() or num_pieces > msmd_roi_sample_max_pieces(): MSMD_ERR_RANGE. */
+int msmd_roi_assign_max_samples(void);
+int msmd_roi_assign_max_classes(void);
+int msmd_roi_assign_gt_chunk(void); /* ground truths per LDS chunk */
+int msmd_roi_sample_max_proposals(void);
+int msmd_roi_sample_max_num(void);
+int msmd_roi_sample_max_pieces(void);
+size_t msmd_roi_assign3d_workspace_bytes(int num_gt);
+int msmd_roi_assign3d_f32(const float* proposals /* [P,7] */,
+                          const int64_t* proposal_labels /* [P] */,
+                          const int32_t* proposal_offsets /* host [batch+1] */,
+                          const float* gt_boxes /* [G,7] */, const int64_t* gt_labels /* [G] */,
+                          const int32_t* gt_offsets /* host [batch+1] */, int batch,
+                          int num_classes, int single, const float* pos_iou_thr /* host */,
+                          const float* neg_iou_thr /* host */,
+                          const float* min_pos_iou /* host */, int32_t* gt_inds /* [P] */,
+                          float* max_overlaps /* [P] */, int64_t* labels /* [P] */,
+                          void* workspace, size_t workspace_bytes, msmd_stream_t stream);
+int msmd_roi_sample_targets_f32(const float* proposals /* [P,7] */,
+                                const int32_t* proposal_offsets /* host [batch+1] */,
+                                const int32_t* gt_inds /* [P] */,
+                                const float* max_overlaps /* [P] */, const float* keys /* [P] */,
+                                const float* gt_boxes /* [G,7] */,
+                                const int32_t* gt_offsets /* host [batch+1] */, int batch,
+                                int num, int num_expected_pos, double neg_pos_ub,
+                                int num_pieces, const double* neg_piece_fractions /* host */,
+                                const float* neg_iou_piece_thrs /* host */, float cls_pos_thr,
+                                float cls_neg_thr, float* rois /* [batch,num,8] */,
+                                float* ious /* [batch,num] */, float* label /* [batch,num] */,
+                                float* label_weights /* [batch,num] */,
+                                int64_t* reg_mask /* [batch,num] */,
+                                float* bbox_weights /* [batch,num] */,
+                                float* pos_gt_bboxes /* [batch,num,7] */,
+                                float* bbox_targets /* [batch,num,7] */,
+                                int32_t* sampled_inds /* [batch,num] */,
+                                int32_t* counts /* [batch,2] */, msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -273,6 +273,17 @@ SIGNATURES = {
     "msmd_h3d_cue_targets_f32": (_i, [_vp] * 10 + [_i] * 6 + [_f] * 6 + [_vp] * 9),
     "msmd_semantic_gt_chunk": (_i, []),
     "msmd_semantic_targets_f32": (_i, [_vp] * 5 + [_i, _vp] + [_i] * 4 + [_vp] * 3),
+    "msmd_roi_assign_max_samples": (_i, []),
+    "msmd_roi_assign_max_classes": (_i, []),
+    "msmd_roi_assign_gt_chunk": (_i, []),
+    "msmd_roi_sample_max_proposals": (_i, []),
+    "msmd_roi_sample_max_num": (_i, []),
+    "msmd_roi_sample_max_pieces": (_i, []),
+    "msmd_roi_assign3d_workspace_bytes": (_sz, [_i]),
+    "msmd_roi_assign3d_f32": (_i, [_vp, _vp, _ip, _vp, _vp, _ip, _i, _i, _i, _fp, _fp, _fp, _vp, _vp,
+                                   _vp, _vp, _sz, _vp]),
+    "msmd_roi_sample_targets_f32": (_i, [_vp, _ip, _vp, _vp, _vp, _vp, _ip, _i, _i, _i, C.c_double,
+                                         _i, C.POINTER(C.c_double), _fp, _f, _f] + [_vp] * 11),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

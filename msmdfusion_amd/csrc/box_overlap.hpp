@@ -1,5 +1,6 @@
 // box_overlap.hpp -- rotated BEV rectangle overlap (ops/iou3d/src/iou3d_kernel.cu:36-242),
-// shared by boxes.hip (the loss side: BaseInstance3DBoxes.overlaps) and nms.hip (rotated NMS).
+// shared by boxes.hip (the loss side: BaseInstance3DBoxes.overlaps), nms.hip (rotated NMS) and
+// roi_targets.hip (Part-A2's 3-D IoU assigner, which must reproduce boxes.hip's values).
 #pragma once
 #include "common.hpp"
 
@@ -121,6 +122,29 @@ __device__ inline float overlap_bev(const Box& a, const Box& b) {
     area += ux * wy - uy * wx;
   }
   return (float)(fabs((double)area) / 2.0);
+}
+
+// LiDARInstance3DBoxes.bev (columns 0,1,3,4,6) -> xywhr2xyxyr
+__device__ __forceinline__ Box bev_of(const float* r) {
+  Box b;
+  const float hw = r[3] / 2.f, hh = r[4] / 2.f;
+  b.v[0] = r[0] - hw;
+  b.v[1] = r[1] - hh;
+  b.v[2] = r[0] + hw;
+  b.v[3] = r[1] + hh;
+  b.v[4] = r[6];
+  return b;
+}
+
+// BaseInstance3DBoxes.overlaps of one pair of 7-column LiDAR rows (base_box3d.py:352-438): BEV
+// overlap x height overlap over the union (iof: over a's volume).  The one place this is
+// written: every kernel that needs the value calls this, so their results agree bit for bit.
+__device__ inline float iou3d_pair(const float* ra, const float* rb, bool iof) {
+  const float top = fminf(ra[2] + ra[5], rb[2] + rb[5]), bot = fmaxf(ra[2], rb[2]);
+  const float oh = fmaxf(top - bot, 0.f);
+  const float inter = overlap_bev(bev_of(ra), bev_of(rb)) * oh;
+  const float va = ra[3] * ra[4] * ra[5], vb = rb[3] * rb[4] * rb[5];
+  return iof ? inter / fmaxf(va, 1e-8f) : inter / fmaxf(va + vb - inter, 1e-8f);
 }
 
 }  // namespace bev

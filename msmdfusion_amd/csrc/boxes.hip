@@ -20,18 +20,6 @@ namespace {
 
 using namespace bev;
 
-// LiDARInstance3DBoxes.bev (columns 0,1,3,4,6) -> xywhr2xyxyr
-__device__ __forceinline__ Box bev_of(const float* r) {
-  Box b;
-  const float hw = r[3] / 2.f, hh = r[4] / 2.f;
-  b.v[0] = r[0] - hw;
-  b.v[1] = r[1] - hh;
-  b.v[2] = r[0] + hw;
-  b.v[3] = r[1] + hh;
-  b.v[4] = r[6];
-  return b;
-}
-
 // mode 0: IoU, 1: IoF (over boxes a), 2: BEV overlap area of 5-column xyxyr boxes
 __global__ __launch_bounds__(256) void boxes_iou3d_kernel(
     const float* __restrict__ a, int lda, const float* __restrict__ b, int ldb,
@@ -58,11 +46,7 @@ __global__ __launch_bounds__(256) void boxes_iou3d_kernel(
     out[t] = overlap_bev(ba, bb);
     return;
   }
-  const float top = fminf(ra[2] + ra[5], rb[2] + rb[5]), bot = fmaxf(ra[2], rb[2]);
-  const float oh = fmaxf(top - bot, 0.f);
-  const float inter = overlap_bev(bev_of(ra), bev_of(rb)) * oh;
-  const float va = ra[3] * ra[4] * ra[5], vb = rb[3] * rb[4] * rb[5];
-  out[t] = mode == 0 ? inter / fmaxf(va + vb - inter, 1e-8f) : inter / fmaxf(va, 1e-8f);
+  out[t] = iou3d_pair(ra, rb, mode == 1);
 }
 
 // one workgroup per box: heat[plane] = max(heat[plane], bump clipped to the map)

@@ -537,6 +537,104 @@ class H3DNet(nn.Module):
         return self.simple_test(points, img_metas, **kw)
 
 
+@DETECTORS.register_module()
+class PartA2(nn.Module):
+    """mmdet3d/models/detectors/parta2.py on two_stage.py (TwoStage3DDetector): hard
+    voxelization, HardSimpleVFE, SparseUNet, SECOND / SECONDFPN, PartA2RPNHead as `rpn_head`
+    (built with train_cfg.rpn / test_cfg.rpn) and PartAggregationROIHead as `roi_head`
+    (train_cfg.rcnn / test_cfg.rcnn), under the reference's attribute names (its state-dict
+    prefixes).  The batch size is the length of the point list, where the reference reads
+    `coors[-1, 0].item() + 1` (:47).  aug_test is not built, as for the other detectors."""
+
+    def __init__(self, voxel_layer, voxel_encoder, middle_encoder, backbone, neck=None,
+                 rpn_head=None, roi_head=None, train_cfg=None, test_cfg=None, pretrained=None,
+                 init_cfg=None):
+        super().__init__()
+        from .registry import build_head
+        sub = lambda cfg, key: None if cfg is None else cfg[key]              # noqa: E731
+        self.backbone = build_backbone(backbone)
+        self.neck = None if neck is None else build_neck(neck)
+        self.rpn_head = rpn_head if isinstance(rpn_head, nn.Module) or rpn_head is None else \
+            build_head(dict(rpn_head, train_cfg=sub(train_cfg, "rpn"),
+                            test_cfg=sub(test_cfg, "rpn")))
+        self.roi_head = roi_head if isinstance(roi_head, nn.Module) or roi_head is None else \
+            build_head(dict(roi_head, train_cfg=sub(train_cfg, "rcnn"),
+                            test_cfg=sub(test_cfg, "rcnn")))
+        self.train_cfg, self.test_cfg = train_cfg, test_cfg
+        self.voxel_layer = Voxelization(**voxel_layer)
+        self.voxel_encoder = build_voxel_encoder(voxel_encoder)
+        self.middle_encoder = build_middle_encoder(middle_encoder)
+
+    with_neck = property(lambda self: self.neck is not None)
+    with_rpn = property(lambda self: self.rpn_head is not None)
+    with_roi_head = property(lambda self: self.roi_head is not None)
+
+    @torch.no_grad()
+    def voxelize(self, points):
+        """parta2.py:56-85: hard voxelization per sample, the batch id prepended, and the voxel
+        centres (semantic_head.voxel_centers)."""
+        from .semantic_head import voxel_centers
+        voxels, nums, coors = [], [], []
+        for b, (v, c, n) in enumerate(self.voxel_layer.forward_batch(points, fused_mean=False)):
+            voxels.append(v)
+            nums.append(n)
+            coors.append(nn.functional.pad(c, (1, 0), mode="constant", value=b))
+        coors = torch.cat(coors, dim=0)
+        return dict(voxels=torch.cat(voxels, dim=0), num_points=torch.cat(nums, dim=0),
+                    coors=coors,
+                    voxel_centers=voxel_centers(coors, self.voxel_layer.voxel_size,
+                                                self.voxel_layer.point_cloud_range))
+
+    def extract_feat(self, points, img_metas=None):
+        """parta2.py:41-54 -> (feats_dict with spatial_features / seg_features / neck_feats,
+        voxel_dict)."""
+        voxel_dict = self.voxelize(points)
+        voxel_features = self.voxel_encoder(voxel_dict["voxels"], voxel_dict["num_points"],
+                                            voxel_dict["coors"])
+        feats_dict = self.middle_encoder(voxel_features, voxel_dict["coors"], len(points))
+        x = self.backbone(feats_dict["spatial_features"])
+        if self.with_neck:
+            feats_dict.update({"neck_feats": self.neck(x)})
+        return feats_dict, voxel_dict
+
+    def forward_train(self, points, img_metas=None, gt_bboxes_3d=None, gt_labels_3d=None,
+                      gt_bboxes_ignore=None, proposals=None, generator=None):
+        """parta2.py:87-134 -> the losses of the RPN head, the semantic head and the bbox head.
+        generator: the torch.Generator of the RoI sampler's keys."""
+        feats_dict, voxels_dict = self.extract_feat(points, img_metas)
+        metas = img_metas if img_metas is not None else [None] * len(points)
+        losses = dict()
+        if self.with_rpn:
+            rpn_outs = self.rpn_head(feats_dict["neck_feats"])
+            losses.update(self.rpn_head.loss(*rpn_outs, gt_bboxes_3d, gt_labels_3d, metas,
+                                             gt_bboxes_ignore=gt_bboxes_ignore))
+            proposal_cfg = self.train_cfg.get("rpn_proposal", self.test_cfg["rpn"])
+            with torch.no_grad():
+                proposal_list = self.rpn_head.get_bboxes(*rpn_outs, metas, proposal_cfg)
+        else:
+            proposal_list = proposals
+        losses.update(self.roi_head.forward_train(feats_dict, voxels_dict, metas, proposal_list,
+                                                  gt_bboxes_3d, gt_labels_3d,
+                                                  generator=generator))
+        return losses
+
+    def simple_test(self, points, img_metas=None, proposals=None, rescale=False):
+        """parta2.py:136-149."""
+        feats_dict, voxels_dict = self.extract_feat(points, img_metas)
+        metas = img_metas if img_metas is not None else [None] * len(points)
+        if self.with_rpn:
+            rpn_outs = self.rpn_head(feats_dict["neck_feats"])
+            proposal_list = self.rpn_head.get_bboxes(*rpn_outs, metas, self.test_cfg["rpn"])
+        else:
+            proposal_list = proposals
+        return self.roi_head.simple_test(feats_dict, voxels_dict, metas, proposal_list)
+
+    def forward(self, points, img_metas=None, return_loss=False, **kw):
+        if return_loss:
+            return self.forward_train(points, img_metas, **kw)
+        return self.simple_test(points, img_metas, **kw)
+
+
 class MLP(nn.Module):
     """mmdet3d/models/utils/mlp.py: (B, C, N) features through kernel-size-1 ConvModules with a
     conv bias under the norm, keys `mlp.layer{i}.conv.*` / `mlp.layer{i}.bn.*`."""

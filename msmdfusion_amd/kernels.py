@@ -3817,3 +3817,108 @@ def semantic_targets(voxel_centers, batch_ids, gt_boxes, enlarged_boxes, gt_labe
         int(gt_labels.dtype == torch.long), _p(gt_counts), n, b, g, int(num_classes), _p(seg),
         _p(part), _stream()), "msmd_semantic_targets_f32")
     return seg, part
+
+
+# ------------------------------------------------ Part-A2 RoI assignment / sampling (row n10)
+ROI_ASSIGN_MAX_SAMPLES = lib.msmd_roi_assign_max_samples()
+ROI_ASSIGN_MAX_CLASSES = lib.msmd_roi_assign_max_classes()
+ROI_ASSIGN_GT_CHUNK = lib.msmd_roi_assign_gt_chunk()
+ROI_SAMPLE_MAX_PROPOSALS = lib.msmd_roi_sample_max_proposals()
+ROI_SAMPLE_MAX_NUM = lib.msmd_roi_sample_max_num()
+ROI_SAMPLE_MAX_PIECES = lib.msmd_roi_sample_max_pieces()
+
+
+def _roi_lists(proposals, proposal_offsets, gt_boxes, gt_offsets):
+    _need_cuda(proposals, gt_boxes)
+    poffs, goffs = [int(v) for v in proposal_offsets], [int(v) for v in gt_offsets]
+    if len(poffs) != len(goffs) or len(poffs) < 1:
+        raise ValueError("proposal_offsets and gt_offsets hold one entry per sample plus one")
+    for t, offs, what in ((proposals, poffs, "proposals"), (gt_boxes, goffs, "gt_boxes")):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 7 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float32 [n, 7] tensor, got %s %s"
+                             % (what, t.dtype, tuple(t.shape)))
+        if offs[0] != 0 or offs[-1] != t.shape[0] or any(b < a for a, b in zip(offs, offs[1:])):
+            raise ValueError("%s: the offsets must ascend from 0 to %d, got %s"
+                             % (what, t.shape[0], offs))
+    return poffs, goffs
+
+
+def roi_assign3d(proposals, proposal_labels, proposal_offsets, gt_boxes, gt_labels, gt_offsets,
+                 pos_iou_thr, neg_iou_thr, min_pos_iou, single=False):
+    """Class-aware MaxIoUAssigner over the 3-D IoU for every sample of the batch
+    (msmd_roi_assign3d_f32): no IoU matrix, nothing read back.  proposals float32 [P, 7],
+    proposal_labels long [P] (None with single=True), gt_boxes float32 [G, 7], gt_labels long
+    [G]; proposal_offsets / gt_offsets: HOST sequences [B + 1].  Thresholds: one float per class
+    (host), one in all with single=True.
+    -> gt_inds int32 [P] (-1 ignored, 0 background, i + 1 with i local to the sample's list),
+       max_overlaps float32 [P], labels long [P] (-1 where unassigned)."""
+    poffs, goffs = _roi_lists(proposals, proposal_offsets, gt_boxes, gt_offsets)
+    _need_cuda(proposal_labels, gt_labels)
+    batch, p, g = len(poffs) - 1, proposals.shape[0], gt_boxes.shape[0]
+    classes = len(pos_iou_thr)
+    if not (len(neg_iou_thr) == len(min_pos_iou) == classes) or classes < 1:
+        raise ValueError("every threshold list holds one entry per class")
+    if single and classes != 1:
+        raise ValueError("the single-assigner form takes one threshold triple")
+    if not single and (proposal_labels is None or proposal_labels.dtype != torch.long
+                       or proposal_labels.numel() != p or not proposal_labels.is_contiguous()):
+        raise ValueError("proposal_labels must be a contiguous long tensor, one per proposal")
+    if gt_labels.dtype != torch.long or gt_labels.numel() != g or not gt_labels.is_contiguous():
+        raise ValueError("gt_labels must be a contiguous long tensor with one entry per box")
+    dev = proposals.device
+    gt_inds = torch.empty((p,), dtype=torch.int32, device=dev)
+    overlaps = torch.empty((p,), dtype=torch.float32, device=dev)
+    labels = torch.empty((p,), dtype=torch.long, device=dev)
+    nbytes = lib.msmd_roi_assign3d_workspace_bytes(g)
+    ws = _ws(nbytes, dev)
+    check(lib.msmd_roi_assign3d_f32(
+        _p(proposals), None if single else _p(proposal_labels), _host_ints(poffs), _p(gt_boxes),
+        _p(gt_labels), _host_ints(goffs), batch, classes, int(bool(single)),
+        float_arr(pos_iou_thr), float_arr(neg_iou_thr), float_arr(min_pos_iou), _p(gt_inds),
+        _p(overlaps), _p(labels), _p(ws), nbytes, _stream()), "msmd_roi_assign3d_f32")
+    return gt_inds, overlaps, labels
+
+
+def roi_sample_targets(proposals, proposal_offsets, gt_inds, max_overlaps, keys, gt_boxes,
+                       gt_offsets, num, num_expected_pos, neg_pos_ub, neg_piece_fractions,
+                       neg_iou_piece_thrs, cls_pos_thr, cls_neg_thr):
+    """IoUNegPiecewiseSampler.sample + PartA2BboxHead._get_target_single for every sample in one
+    launch (msmd_roi_sample_targets_f32), nothing read back.  gt_inds int32 / max_overlaps
+    float32 [P] as roi_assign3d returns them, keys float32 [P]: random_choice takes the smallest
+    keys, ties to the lower index.
+    -> dict of tensors padded to `num` rows per sample: rois [B, num, 8], iou, label,
+       label_weights, reg_mask (long), bbox_weights [B, num], pos_gt_bboxes, bbox_targets
+       [B, num, 7], inds int32 [B, num] (proposal index in its sample, -1 padding), counts int32
+       [B, 2] = (positives, negatives); a sample's rows are its positives, then its negatives,
+       each ascending."""
+    poffs, goffs = _roi_lists(proposals, proposal_offsets, gt_boxes, gt_offsets)
+    _need_cuda(gt_inds, max_overlaps, keys)
+    batch, p = len(poffs) - 1, proposals.shape[0]
+    for t, dtype, what in ((gt_inds, torch.int32, "gt_inds"),
+                           (max_overlaps, torch.float32, "max_overlaps"),
+                           (keys, torch.float32, "keys")):
+        if t.dtype != dtype or t.numel() != p or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous %s tensor with one entry per proposal"
+                             % (what, dtype))
+    pieces = len(neg_piece_fractions)
+    if pieces != len(neg_iou_piece_thrs) or pieces < 1:
+        raise ValueError("neg_piece_fractions and neg_iou_piece_thrs hold one entry per piece")
+    num = int(num)
+    dev = proposals.device
+
+    def out(shape, dtype=torch.float32):
+        return torch.empty((batch, num) + shape, dtype=dtype, device=dev)
+
+    res = dict(rois=out((8,)), iou=out(()), label=out(()), label_weights=out(()),
+               reg_mask=out((), torch.long), bbox_weights=out(()), pos_gt_bboxes=out((7,)),
+               bbox_targets=out((7,)), inds=out((), torch.int32),
+               counts=torch.empty((batch, 2), dtype=torch.int32, device=dev))
+    fractions = (C.c_double * pieces)(*[float(v) for v in neg_piece_fractions])
+    check(lib.msmd_roi_sample_targets_f32(
+        _p(proposals), _host_ints(poffs), _p(gt_inds), _p(max_overlaps), _p(keys), _p(gt_boxes),
+        _host_ints(goffs), batch, num, int(num_expected_pos), float(neg_pos_ub), pieces, fractions,
+        float_arr(neg_iou_piece_thrs), float(cls_pos_thr), float(cls_neg_thr), _p(res["rois"]),
+        _p(res["iou"]), _p(res["label"]), _p(res["label_weights"]), _p(res["reg_mask"]),
+        _p(res["bbox_weights"]), _p(res["pos_gt_bboxes"]), _p(res["bbox_targets"]),
+        _p(res["inds"]), _p(res["counts"]), _stream()), "msmd_roi_sample_targets_f32")
+    return res

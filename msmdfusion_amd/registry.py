@@ -60,6 +60,7 @@ DETECTORS = Registry("detector")
 ROI_EXTRACTORS = Registry("roi_extractor")
 HEADS = Registry("head")
 FUSION_LAYERS = Registry("fusion_layer")
+BBOX_SAMPLERS = Registry("bbox_sampler")
 
 CONV_LAYERS.register_module("Conv1d", module=nn.Conv1d)
 CONV_LAYERS.register_module("Conv2d", module=nn.Conv2d)
@@ -194,11 +195,19 @@ def build_head(cfg, **kwargs):
     Anchor3DHead (anchor_head.py), FreeAnchor3DHead (free_anchor_head.py), VoteHead /
     BaseConvBboxHead (vote_head.py), SSD3DHead (ssd3d_head.py), PrimitiveHead
     (primitive_head.py), H3DBboxHead / H3DRoIHead (h3d_head.py), PointwiseSemanticHead
-    (semantic_head.py), PartA2RPNHead (parta2_rpn_head.py), TransFusionHead (head.py) and,
+    (semantic_head.py), PartA2RPNHead (parta2_rpn_head.py), PartA2BboxHead
+    (parta2_bbox_head.py), PartAggregationROIHead (parta2_roi_head.py), TransFusionHead (head.py) and,
     for a TransFusionHead config with fuse_img=True, TransFusionHeadLC (fusion_head.py): the
     reference has one class for both, so its config dicts build unchanged."""
     from . import (anchor_head, center_head, free_anchor_head, fusion_head, h3d_head,  # noqa: F401
-                   head, parta2_rpn_head, primitive_head, semantic_head, ssd3d_head, vote_head)
+                   head, parta2_bbox_head, parta2_roi_head, parta2_rpn_head, primitive_head,
+                   semantic_head, ssd3d_head, vote_head)
     if isinstance(cfg, dict) and cfg.get("type") == "TransFusionHead" and cfg.get("fuse_img"):
         cfg = dict(cfg, type="TransFusionHeadLC")
     return HEADS.build(cfg, **kwargs)
+
+
+def build_sampler(cfg):
+    """mmdet.core.build_sampler for the RoI heads: IoUNegPiecewiseSampler (parta2_roi_head.py)."""
+    from . import parta2_roi_head  # noqa: F401
+    return cfg if not isinstance(cfg, dict) else BBOX_SAMPLERS.build(cfg)
